@@ -3,6 +3,7 @@
 TemporalModelOptimized1f lifter on MI355X (BASELINE.json configs 2 and 4).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--global-batch 65536 | --batch B] [--dtype f16x3]
+                    [--full] [--dump-outputs DIR]
 
 One step = one eval-mode forward of the global batch of 243-frame windows (65,536 by
 default: config 4), sharded over the N ranks by vp3d_amd.shard.shard_range, every
@@ -12,7 +13,13 @@ split-fp16 path (f16x3: the north-star MPJPE tolerance at 16-bit MFMA rates).
 `value` = G*K / max-over-ranks(wall time of K steps).  --batch B instead gives every
 rank its own B windows (weak scaling).
 
-At N = 1 the line also carries, each with its own roofline, parity and CPU baseline:
+A plain run does only that: set-up, W warm-up steps, the K timed steps, one JSON line with
+the contract fields (metric, value, unit, ms_per_step, dtype, ...).  --dump-outputs DIR also
+writes the poses of the last timed step as DIR/poses_3d.npy (float32; the inputs are seeded,
+so two builds can be compared output for output).  Everything below takes passes of its own
+and is behind --full.
+
+With --full, at N = 1 the line also carries, each with its own roofline, parity and CPU baseline:
   bf16, fp32    config 2's dtype and the exact parity path on the same windows
   batch_sweep_poses_per_s   B = 1,024 / 8,192 / 65,536 in f16x3 and bf16
   config3       trajectory-conditioned windows (K.E + gather + concat in the step): fp16,
@@ -22,7 +29,7 @@ At N = 1 the line also carries, each with its own roofline, parity and CPU basel
                 p50 / p90 / p99)
   sequence      the dilated TemporalModel over one 65,778-frame sequence (run.py --evaluate's
                 shape) in f16x3 and fp32 (the gate) and bf16, with ΔMPJPE vs the oracle
-Besides the JSON contract fields the line carries
+Besides the JSON contract fields the --full line carries
   roofline      dominant kernel (block-1 k3 conv GEMM) FLOP per launch / its average
                 HIP-event duration on the launch stream during the timed steps; traffic =
                 the committed PMC summary of the same build (null if the build differs)
@@ -71,9 +78,19 @@ def parse():
                          "fp16 (--traj, --stream)")
     ap.add_argument("--sweep", type=lambda v: [int(t) for t in v.split(",") if t], default=[1024, 8192, 65536],
                     help="config-2 batch sweep on one GPU (windows per step)")
+    ap.add_argument("--full", action="store_true",
+                    help="configs 2-4: besides the headline figure, the per-layer pass, roofline and parity of the "
+                         "timed dtype and, at N = 1, every leg (the other dtypes, the batch sweep, configs 3 and 5, "
+                         "the sequence mode) and the CPU baseline; without it the run sets up, warms up, times "
+                         "--steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed (the arrays the caller "
+                         "of the timed path receives) as DIR/<name>.npy, float32 / float64, at most 64 MB in all")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip every leg (the other dtypes, the sweep, configs 3 and 5) and the CPU baseline")
-    ap.add_argument("--no-legs", action="store_true", help="skip the config-3 and config-5 legs of the default line")
+                    help="with --full: skip every leg (the other dtypes, the sweep, configs 3 and 5) and the CPU "
+                         "baseline")
+    ap.add_argument("--no-legs", action="store_true",
+                    help="with --full: skip the config-3 and config-5 legs of the default line")
     ap.add_argument("--pregathered", action="store_true",
                     help="configs 2/4: time the forward over a window tensor gathered once before the "
                          "timed region (the reference's form: batch built outside the model) instead of "
@@ -110,6 +127,31 @@ def synth_windows(B, T, jin, seed, device):
     base = (torch.rand((B, 1, jin, 2), generator=g, device=device) - 0.5) * 1.2
     steps = torch.randn((B, T, jin, 2), generator=g, device=device) * 0.003
     return (base + torch.cumsum(steps, dim=1)).contiguous()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(args, rank, world, arrays):
+    """--dump-outputs DIR: write the device tensors `arrays` (name -> what the last timed step
+    left in the buffers its caller reads) as DIR/<name>.npy (<name>_rank<r>.npy under N > 1
+    ranks), float64 kept, everything else as float32.  Every input of the bench is seeded, so
+    two builds run with the same arguments can be compared array for array.  Above 64 MB in
+    all, each array is cut to a fixed seeded sample of its flattened elements."""
+    if not args.dump_outputs:
+        return
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        host[name] = (t if t.dtype == torch.float64 else t.float()).cpu().numpy()
+    total = sum(a.nbytes for a in host.values())
+    for name, a in host.items():
+        if total > DUMP_LIMIT_BYTES:
+            keep = max(1, int(a.size * (DUMP_LIMIT_BYTES / total)))
+            a = a.reshape(-1)[np.sort(np.random.RandomState(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(args.dump_outputs, name + (f"_rank{rank}" if world > 1 else "") + ".npy"),
+                np.ascontiguousarray(a))
 
 
 def stream_traffic(mode):
@@ -170,6 +212,7 @@ def stream_main(args, world, rank, dev, emit=True):
     dt = time.perf_counter() - t0
     ev_ms = ev0.elapsed_time(ev1)
     args.steps = n_launch * G  # steps actually timed (whole graphs)
+    dump_outputs(args, rank, world, {"poses_3d": pr})  # the pose ring: the last Q steps' poses
     if world > 1:
         tt = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -365,6 +408,7 @@ def train_main(args, world, rank, dev):
         tt = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    dump_outputs(args, rank, world, {"loss": loss.reshape(1)})
     if rank != 0:
         return
     fwd, wg, dg = train_flop_per_window(RF)
@@ -469,6 +513,7 @@ def seq_main(args, world, rank, dev):
         tt = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    dump_outputs(args, rank, world, {"poses_3d": y})
     if rank != 0:
         return
     flop = seq_flop_per_pose(kind)
@@ -603,6 +648,7 @@ def sequence_main(args, world, rank, dev):
         tt = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    dump_outputs(args, rank, world, {"poses_3d": case.y})
     if rank != 0:
         return
     T_out = case.T_out
@@ -891,13 +937,17 @@ class WindowsCase:
                 lifter.forward(x, dtype, out=y)
         return step
 
-    def run(self, dtype, steps, warmup, settle_s, world):
-        """Time `steps` steps in `dtype`; returns (seconds, per-layer ms, dominant record, output)."""
+    def run(self, dtype, steps, warmup, settle_s, world, profile=True):
+        """Time `steps` steps in `dtype`; returns (seconds, per-layer ms, dominant record, output).
+        profile=False: the timed steps alone, no per-layer pass and no events (both records None)."""
         y = torch.empty((self.B, 1, JOINTS, 3), device=self.dev)
         self.lifter.reserve(self.B, self.RF, dtype)
+        step = self.make_step(dtype, y, x=self.x)
         with torch.no_grad():
-            dt, per_layer, dom = profiled_run(self.lifter, self.make_step(dtype, y, x=self.x), steps, warmup,
-                                              settle_s, world)
+            if profile:
+                dt, per_layer, dom = profiled_run(self.lifter, step, steps, warmup, settle_s, world)
+            else:
+                dt, per_layer, dom = timed_steps(step, steps, warmup, settle_s, world), None, None
         # a device-side fault of any forward of the leg (split-K timeout, f16x3 range) raises here
         self.lifter.sync_status()
         return dt, per_layer, dom, y
@@ -975,25 +1025,25 @@ def windows_main(args, world, rank, dev):
     Default line: a global batch of --global-batch windows (65,536: config 4) sharded over the
     ranks with vp3d_amd.shard.shard_range (strong scaling; N = 1 is the config-2/4 single-GPU
     point), timed in the accurate split-fp16 path (f16x3: the north-star tolerance at MFMA
-    rates).  --batch B: B windows per rank (weak scaling).  At N = 1 the line also carries
-    the bf16 (config 2's dtype) and fp32 legs, the batch sweep, config 3 (fp16 / f16x3 / fp32)
-    and config 5 (causal streaming) as legs, each with its roofline, parity and CPU baseline."""
+    rates).  --batch B: B windows per rank (weak scaling).  Without --full that is the whole
+    run; with it the line gains the timed dtype's roofline, per-layer times and parity, and at
+    N = 1 also carries the bf16 (config 2's dtype) and fp32 legs, the batch sweep, config 3
+    (fp16 / f16x3 / fp32) and config 5 (causal streaming) as legs, each with its roofline,
+    parity and CPU baseline."""
     traj = args.traj
     dtype = args.dtype or ("fp16" if traj else "f16x3")
     case = WindowsCase(traj, args.global_batch, rank, world, dev, args.batch, args.pregathered)
     G, B = case.G, case.B
-    dt, per_layer, dom, y = case.run(dtype, args.steps, args.warmup, args.settle_seconds, world)
+    dt, per_layer, dom, y = case.run(dtype, args.steps, args.warmup, args.settle_seconds, world, profile=args.full)
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     value = G * args.steps / dt if case.scaling == "strong" else world * B * args.steps / dt
+    # what the caller of the timed step receives: this rank's (B, 1, 17, 3) poses of the last step
+    dump_outputs(args, rank, world, {"poses_3d": y})
     if rank != 0:
         return
-    P = args.parity_windows
-    parity = dict(case.parity_info(P), **{f"{dtype}_{k}": v for k, v in case.parity(y, P).items()})
-    del y
-    traffic, tnote = committed_traffic(dtype, B, traj)
     out = {
         "metric": METRIC, "value": round(value, 2), "unit": "poses/s", "n_gpus": world, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True,
@@ -1014,14 +1064,27 @@ def windows_main(args, world, rank, dev):
             if case.scaling == "strong" else f"dp{world} (independent windows per rank, no collective)",
             "flop_per_pose": case.flop_pose},
         "tflops_effective": round(value * case.flop_pose / 1e12, 2),
-        "roofline": roofline_of(dom, PEAK_TFLOPS[dtype], traffic, tnote),
-        "per_layer_ms": per_layer,
-        "per_layer_note": "untimed pass with HIP events around every launch",
         "faults": 0,
         "faults_note": "vp3d_sync_status after every timed leg: a device-side fault (split-K timeout, f16x3 "
                        "range) raises instead of reporting",
-        "parity": parity,
     }
+    if not args.full:
+        # the plain run: the headline figure alone (roofline, per-layer times, parity, the legs
+        # and the CPU baseline take passes of their own: --full)
+        del y
+        case.close()
+        emit_line(out)
+        return
+    P = args.parity_windows
+    parity = dict(case.parity_info(P), **{f"{dtype}_{k}": v for k, v in case.parity(y, P).items()})
+    del y
+    traffic, tnote = committed_traffic(dtype, B, traj)
+    out.update({
+        "roofline": roofline_of(dom, PEAK_TFLOPS[dtype], traffic, tnote),
+        "per_layer_ms": per_layer,
+        "per_layer_note": "untimed pass with HIP events around every launch",
+        "parity": parity,
+    })
     if dtype == "f16x3":
         out["roofline"]["peak_note"] = ("f16 dense MFMA peak / 3: three f16 products per algorithmic "
                                         "multiply-add (hi.hi + hi.lo + lo.hi)")

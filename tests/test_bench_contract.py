@@ -95,7 +95,7 @@ def test_bench_cli_parses():
     out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--help"], capture_output=True,
                          text=True, timeout=300)
     assert out.returncode == 0, out.stderr
-    for flag in ("--gpus", "--steps", "--warmup", "--global-batch", "--traj", "--stream"):
+    for flag in ("--gpus", "--steps", "--warmup", "--global-batch", "--traj", "--stream", "--full", "--dump-outputs"):
         assert flag in out.stdout, flag
 
 
@@ -141,6 +141,65 @@ def test_emit_line_puts_headline_keys_last(capsys):
                      "cpu_baseline": {}, "faults": 0})
     keys = list(json.loads(capsys.readouterr().out).keys())
     assert keys == ["metric", "value", "config5", "roofline", "cpu_baseline", "faults", "parity"]
+
+
+def test_dump_outputs_writes_npy(tmp_path, monkeypatch):
+    """--dump-outputs: one DIR/<name>.npy per array, float64 kept and the rest as float32,
+    per-rank names under N > 1 ranks; above the size limit a fixed seeded sample."""
+    sys.path.insert(0, REPO)
+    import argparse
+    import numpy as np
+    import torch
+    import bench
+    y = (torch.arange(24, dtype=torch.float32) / 8).reshape(4, 1, 2, 3).to(torch.float16)
+    z = torch.linspace(0, 1, 5, dtype=torch.float64)
+    bench.dump_outputs(argparse.Namespace(dump_outputs=None), 0, 1, {"poses_3d": y})  # off: writes nothing
+    assert not list(tmp_path.iterdir())
+    a = argparse.Namespace(dump_outputs=str(tmp_path / "one"))
+    bench.dump_outputs(a, 0, 1, {"poses_3d": y, "z": z})
+    got = np.load(tmp_path / "one" / "poses_3d.npy")
+    assert got.dtype == np.float32 and got.shape == (4, 1, 2, 3) and np.array_equal(got, y.float().numpy())
+    gz = np.load(tmp_path / "one" / "z.npy")
+    assert gz.dtype == np.float64 and np.array_equal(gz, z.numpy())
+    a = argparse.Namespace(dump_outputs=str(tmp_path / "two"))
+    bench.dump_outputs(a, 1, 2, {"poses_3d": y})
+    assert sorted(p.name for p in (tmp_path / "two").iterdir()) == ["poses_3d_rank1.npy"]
+    # 96 + 40 bytes against a limit of 68: half of every array, the same elements every time
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 68)
+    for d in ("three", "four"):
+        bench.dump_outputs(argparse.Namespace(dump_outputs=str(tmp_path / d)), 0, 1, {"poses_3d": y, "z": z})
+    s3, s4 = np.load(tmp_path / "three" / "poses_3d.npy"), np.load(tmp_path / "four" / "poses_3d.npy")
+    assert s3.shape == (12,) and np.array_equal(s3, s4) and np.isin(s3, y.float().numpy()).all()
+    assert s3.nbytes + np.load(tmp_path / "three" / "z.npy").nbytes <= 68
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """A plain run on a small global batch: exactly --steps timed steps, the contract fields and
+    none of the --full figures, and --dump-outputs holds the last step's poses -- the same
+    arrays from a second run (seeded inputs), finite, float32."""
+    import numpy as np
+    runs = []
+    for d in ("a", "b"):
+        r = _bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--global-batch", "300", "--settle-seconds", "0",
+                    "--dump-outputs", str(tmp_path / d)], {})
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        runs.append((json.loads(lines[0]), np.load(tmp_path / d / "poses_3d.npy")))
+    line, y = runs[0]
+    with open(os.path.join(REPO, "BASELINE.json")) as f:
+        assert line["metric"] == json.load(f)["metric"]
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["n_gpus"] == 1 and line["dtype"] == "f16x3"
+    assert line["unit"] == "poses/s" and line["higher_is_better"] is True and line["faults"] == 0
+    assert line["value"] == pytest.approx(300 / (line["ms_per_step"] * 1e-3), rel=1e-3)
+    for k in ("roofline", "per_layer_ms", "parity", "cpu_baseline", "bf16", "fp32", "config3", "config5", "sequence"):
+        assert k not in line, k
+    assert y.dtype == np.float32 and y.shape == (300, 1, 17, 3) and np.isfinite(y).all() and np.abs(y).max() > 0
+    assert [p.name for p in (tmp_path / "a").iterdir()] == ["poses_3d.npy"]
+    # same arguments, same inputs: the two runs agree to the f16x3 path's own run-to-run rounding
+    # (split-K partial sums may land in either order: a few ulps of f32 on ~0.1 m outputs)
+    assert np.abs(runs[1][1] - y).max() <= 1e-5
 
 
 def test_cpu_baseline_child_pins_threads():

@@ -3,7 +3,7 @@
 # ("old": `git worktree add tools/ab_old <rev>` + its build, done on the CPU side first).
 # Runs the given GPU tests once (new tree), then alternates new / old bench runs.
 # usage: bash tools/ab.sh <tag> "<pytest paths or ''>" "<bench args>" [rounds]
-#   e.g. bash tools/ab.sh x3epi "tests/test_gpu_lifter.py" "--dtype f16x3 --steps 20 --no-extras --no-legs" 2
+#   e.g. bash tools/ab.sh x3epi "tests/test_gpu_lifter.py" "--full --dtype f16x3 --steps 20 --no-extras --no-legs" 2
 set -o pipefail
 tag=${1:?tag}; tests=$2; bargs=${3:?bench args}; rounds=${4:-2}
 O=gpurun_out/ab_$tag

@@ -14,9 +14,9 @@ done
 for r in 1 2; do
   for m in def ring; do
     if [ $m = ring ]; then export VP3D_X3_EXPAND_RING=1; else unset VP3D_X3_EXPAND_RING; fi
-    timeout -k 10 200 python bench.py --no-extras --steps 10 --warmup 3 > $O/c4_${m}_$r.log 2>&1 || { echo "bench $m failed"; tail -5 $O/c4_${m}_$r.log; exit 1; }
+    timeout -k 10 200 python bench.py --full --no-extras --steps 10 --warmup 3 > $O/c4_${m}_$r.log 2>&1 || { echo "bench $m failed"; tail -5 $O/c4_${m}_$r.log; exit 1; }
     echo "r${r}_c4_$m: $(python tools/bench_brief.py $O/c4_${m}_$r.log)"
-    timeout -k 10 200 python bench.py --no-extras --steps 20 --warmup 3 --global-batch 8192 > $O/c8k_${m}_$r.log 2>&1 || { echo "bench 8k $m failed"; tail -5 $O/c8k_${m}_$r.log; exit 1; }
+    timeout -k 10 200 python bench.py --full --no-extras --steps 20 --warmup 3 --global-batch 8192 > $O/c8k_${m}_$r.log 2>&1 || { echo "bench 8k $m failed"; tail -5 $O/c8k_${m}_$r.log; exit 1; }
     echo "r${r}_8k_$m: $(python tools/bench_brief.py $O/c8k_${m}_$r.log)"
   done
 done

@@ -20,22 +20,22 @@ check)
   [ $rc -ne 0 ] && exit $rc
   timeout -k 10 120 python __graft_entry__.py smoke > $O/smoke.log 2>&1 || { echo smoke failed; tail -5 $O/smoke.log; exit 1; }
   echo "smoke: $(tail -1 $O/smoke.log)"
-  timeout -k 10 600 python bench.py > $O/bench_default.log 2>&1 || { echo bench failed; tail -5 $O/bench_default.log; exit 1; }
+  timeout -k 10 600 python bench.py --full > $O/bench_default.log 2>&1 || { echo bench failed; tail -5 $O/bench_default.log; exit 1; }
   python tools/bench_brief.py $O/bench_default.log
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python bench.py --steps 10 --warmup 3 --no-extras > $O/prof.log 2>&1 || exit $?
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python bench.py --full --steps 10 --warmup 3 --no-extras > $O/prof.log 2>&1 || exit $?
   echo "prof ok"
   ;;
 pmc)
   for spec in "f16x3:" "bf16:" "fp32:" "fp16:--traj" "f16x3:--traj" "fp32:--traj"; do
     dt=${spec%%:*}; ex=${spec#*:}; tag=${dt}${ex:+_traj}
     for C in FETCH_SIZE WRITE_SIZE; do
-      timeout -s KILL 200 rocprofv3 --pmc $C --output-format csv -d $O/$tag/pmc_$C -o run -- python bench.py --dtype $dt $ex --steps 3 --warmup 1 --no-extras --parity-windows 4 --settle-seconds 0.1 > $O/${tag}_$C.log 2>&1 || { echo "$tag $C failed"; tail -3 $O/${tag}_$C.log; exit 1; }
+      timeout -s KILL 200 rocprofv3 --pmc $C --output-format csv -d $O/$tag/pmc_$C -o run -- python bench.py --full --dtype $dt $ex --steps 3 --warmup 1 --no-extras --parity-windows 4 --settle-seconds 0.1 > $O/${tag}_$C.log 2>&1 || { echo "$tag $C failed"; tail -3 $O/${tag}_$C.log; exit 1; }
       echo "$tag $C ok"
     done
   done
   ;;
 modes)
-  timeout -k 10 400 python bench.py --traj --steps 20 --warmup 5 > $O/bench_traj.log 2>&1 || exit 1
+  timeout -k 10 400 python bench.py --full --traj --steps 20 --warmup 5 > $O/bench_traj.log 2>&1 || exit 1
   echo "traj:   $(python tools/bench_brief.py $O/bench_traj.log)"
   timeout -k 10 300 python bench.py --stream --steps 4096 --warmup 256 --cpu-seconds 5 > $O/bench_stream.log 2>&1 || exit 1
   echo "stream: $(tail -1 $O/bench_stream.log | cut -c1-300)"

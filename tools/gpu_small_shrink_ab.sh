@@ -13,7 +13,7 @@ for r in 1 2; do
   for m in split f32; do
     if [ $m = f32 ]; then export VP3D_X3_SHRINK=f32; else unset VP3D_X3_SHRINK; fi
     for b in 8192 1024; do
-      timeout -k 10 200 python bench.py --no-extras --steps 40 --warmup 5 --global-batch $b > $O/b${b}_${m}_$r.log 2>&1 || { echo "bench $b $m failed"; tail -5 $O/b${b}_${m}_$r.log; exit 1; }
+      timeout -k 10 200 python bench.py --full --no-extras --steps 40 --warmup 5 --global-batch $b > $O/b${b}_${m}_$r.log 2>&1 || { echo "bench $b $m failed"; tail -5 $O/b${b}_${m}_$r.log; exit 1; }
       echo "r${r}_${b}_$m: $(python tools/bench_brief.py $O/b${b}_${m}_$r.log)"
     done
   done

@@ -16,7 +16,7 @@ for r in 1 2; do
       timeout -k 10 200 python bench.py --sequence --dtype $dt --steps 10 --warmup 3 --cpu-seconds 0 > $O/seq_${dt}_${m}_$r.log 2>&1 || { echo "seq $dt $m failed"; tail -5 $O/seq_${dt}_${m}_$r.log; exit 1; }
       echo "r${r}_seq_${dt}_rbw$m: $(python tools/bench_brief.py $O/seq_${dt}_${m}_$r.log)"
     done
-    timeout -k 10 200 python bench.py --no-extras --steps 10 --warmup 3 > $O/c4_${m}_$r.log 2>&1 || { echo "c4 $m failed"; exit 1; }
+    timeout -k 10 200 python bench.py --full --no-extras --steps 10 --warmup 3 > $O/c4_${m}_$r.log 2>&1 || { echo "c4 $m failed"; exit 1; }
     echo "r${r}_c4_rbw$m: $(python tools/bench_brief.py $O/c4_${m}_$r.log)"
   done
 done

@@ -12,7 +12,7 @@ tail -2 $O/pytest.log
 for r in 1 2; do
   for m in split f32; do
     if [ $m = f32 ]; then export VP3D_X3_SHRINK=f32; else unset VP3D_X3_SHRINK; fi
-    timeout -k 10 200 python bench.py --no-extras --steps 10 --warmup 3 > $O/c4_${m}_$r.log 2>&1 || { echo "bench c4 $m failed"; tail -5 $O/c4_${m}_$r.log; exit 1; }
+    timeout -k 10 200 python bench.py --full --no-extras --steps 10 --warmup 3 > $O/c4_${m}_$r.log 2>&1 || { echo "bench c4 $m failed"; tail -5 $O/c4_${m}_$r.log; exit 1; }
     echo "r${r}_c4_$m: $(python tools/bench_brief.py $O/c4_${m}_$r.log)"
     timeout -k 10 200 python bench.py --sequence --dtype f16x3 --steps 10 --warmup 3 --cpu-seconds 0 > $O/seq_${m}_$r.log 2>&1 || { echo "bench seq $m failed"; tail -5 $O/seq_${m}_$r.log; exit 1; }
     echo "r${r}_seq_$m: $(python tools/bench_brief.py $O/seq_${m}_$r.log)"
