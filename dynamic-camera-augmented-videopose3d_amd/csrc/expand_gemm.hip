@@ -29,6 +29,7 @@
 //   * the chunk loop ends on a raw barrier with a counted vmcnt (the weight DMA of the
 //     next chunk only): the output stores stay in flight across chunks.
 #include <cstdlib>
+#include <type_traits>
 
 #include "gemm_common.h"
 
@@ -505,6 +506,382 @@ __global__ __launch_bounds__(256, (X3 && RING == 1) ? 3 : 2) void expand_gemm_h1
     }
 }
 
+// The input-row loader of expand_gemm_h16<.., X3> as a function (the weight-stationary kernel's;
+// the chunked kernel keeps its own text, so its tuned code is what was measured): input row m
+// as f32, per lane the 8 values k = 32 ks + 8 (l >> 4) .. + 7 of the k-slabs [KS0, KS1) of NKS,
+// handed to put(ks, v); what it hands over for k >= K (the last k-slab only) is not defined: the
+// caller zeroes it once the loads have landed, not here.  m < M (the caller clamps).
+// GATHER: the row's window is located by the caller (off, len: its sequence's first frame and
+// length; f0: the row's first frame in it, before clamping).
+template <int NKS, int KS0, int KS1, bool GATHER, typename Put>
+__device__ __forceinline__ void exp_x3_load_row(const ConvGemmParams& p, const GatherSrc& g, int m, int64_t off, int len,
+                                                int f0, int lane, Put&& put) {
+    constexpr float kBias = 0.f;  // (no folded-shift column in the split-fp16 weights)
+    const float* X = (const float*)p.A;
+    if constexpr (!GATHER) {
+        const float* row = X + (int64_t)src_row(p, m) * p.lda;
+#pragma unroll
+        for (int ks = KS0; ks < KS1; ++ks) {
+            const int k0 = ks * 32 + (lane >> 4) * 8;
+            float v[8];
+#pragma unroll
+            for (int e = 0; e < 8; e += 2) {
+                // K even: pairs are wholly in or out; out-of-range pairs read pair 0
+                const bool in = k0 + e < p.K;
+                const float2 x = *(const float2*)(row + (in ? k0 + e : 0));
+                v[e] = x.x;
+                v[e + 1] = x.y;
+            }
+            put(ks, v);
+        }
+    } else {
+        // no camera concat and no clamped frame in the row (the common case): the
+        // row's K values are contiguous in the sequence, one base address per row.
+        // Only the last k-slab holds k >= K (K + 2 > 32 (NKS - 1) and K even).
+        const bool flat = g.cams == nullptr && f0 >= 0 && f0 + p.K / p.lda <= len;
+        if (__all(flat)) {
+            const float* row = g.kps + (off + f0) * g.f2;
+#pragma unroll
+            for (int ks = KS0; ks < KS1; ++ks) {
+                const int k0 = ks * 32 + (lane >> 4) * 8;
+                float v[8];
+#pragma unroll
+                for (int e = 0; e < 8; e += 2) {
+                    const int k = k0 + e;
+                    if (ks + 1 < NKS) {
+                        const float2 x = *(const float2*)(row + k);
+                        v[e] = x.x;
+                        v[e + 1] = x.y;
+                    } else {
+                        const bool in = k < p.K;
+                        const float2 x = *(const float2*)(row + (in ? k : 0));
+                        v[e] = x.x;
+                        v[e + 1] = x.y;
+                    }
+                }
+                put(ks, v);
+            }
+            return;
+        }
+        // tap = k / lda without an integer division: k < 2^12 and lda <= 2^11, so
+        // (k + 0.5) * (1 / lda) stays > 1/(4 lda) away from the next integer
+        const float inv_lda = 1.0f / (float)p.lda;
+        // (the rare path: its per-k taps and columns are recomputed here on every call, not
+        // hoisted out of the caller's row loop into registers it has no room for)
+        int kl = (lane >> 4) * 8;
+        asm volatile("" : "+v"(kl));
+#pragma unroll
+        for (int ks = KS0; ks < KS1; ++ks) {
+            const int k0 = ks * 32 + kl;
+            float v[8];
+#pragma unroll
+            for (int e = 0; e < 8; e += 2) {
+                // lda, f2 and K even: a pair never straddles a tap or the kps|cams edge
+                const int k = k0 + e;
+                const bool in = k < p.K;
+                const float t1 = k == p.K ? kBias : 0.f;
+                const int tap = in ? (int)(((float)k + 0.5f) * inv_lda) : 0;
+                const int c = in ? k - tap * p.lda : 0;
+                int fr = f0 + tap;
+                fr = fr < 0 ? 0 : (fr >= len ? len - 1 : fr);
+                const int64_t gf = off + fr;
+                const float* src = c < g.f2 ? g.kps + gf * g.f2 + c : g.cams + gf * 12 + (c - g.f2);
+                const float2 tv = *(const float2*)src;
+                v[e] = in ? tv.x : t1;
+                v[e + 1] = in ? tv.y : t1;
+            }
+            put(ks, v);
+        }
+    }
+}
+
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef int i32x2 __attribute__((ext_vector_type(2)));
+
+// The epilogue of expand_gemm_h16<.., X3> as a function (the weight-stationary kernel's; the
+// chunked kernel keeps its own text), one 16-row block x 64 channels (acc[j] of a lane: channels
+// n0 + 16 j + 4 (l >> 4) + 0..3 of row 16 rb + (l & 15) of the rows y_rsrc starts at; sc / sh: the
+// lane's scale / shift pairs): BN affine + ReLU, split, whole-line stores; vmax gathers |x| of what
+// it splits (gemm::x3_range_flag).  abl: the measurement builds' switches (0 otherwise).
+template <bool NT>
+__device__ __forceinline__ void exp_x3_epilogue(const f32x4 (&acc)[4], const f32x2 (&sc)[4][2], const f32x2 (&sh)[4][2],
+                                                float& vmax, __amdgpu_buffer_rsrc_t y_rsrc, int rb, int n0, int ldy,
+                                                int lane, int abl) {
+    const int grp = lane >> 4;
+    const int c0 = 8 * ((grp & 1) * 2 + (grp >> 1));
+    const int r16 = lane & 15;
+    const bool top = r16 < 8;
+#pragma unroll
+    for (int jp = 0; jp < 2; ++jp) {
+        // BN affine as ATen forms it (x * scale, then + shift: two roundings, packed
+        // v_pk_mul_f32 / v_pk_add_f32) + ReLU as an integer max on the f32 bits
+        // (negative and -0 -> +0, as x > 0 ? x : 0) in the accumulator layout (lane:
+        // channels n0 + 16 j + 4 (l >> 4) + 0..3 of row 16 rb + (l & 15))
+        float x[4], y[4];
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+#pragma unroll
+            for (int hp = 0; hp < 2; ++hp) {
+                const int j = 2 * jp + q;
+                f32x2 t = f32x2{acc[j][2 * hp], acc[j][2 * hp + 1]} * sc[j][hp];
+                t = t + sh[j][hp];
+                i32x2 ti = __builtin_bit_cast(i32x2, t);  // (the X3 expand is always BN + ReLU)
+                ti = __builtin_elementwise_max(ti, i32x2{0, 0});
+                t = __builtin_bit_cast(f32x2, ti);
+                float* d = q ? y : x;
+                d[2 * hp] = t[0];
+                d[2 * hp + 1] = t[1];
+            }
+        }
+        // blocks 2 jp, 2 jp + 1 -> 8 consecutive channels n0 + 32 jp + c0 + 0..7 per
+        // lane (the x values just written by VALU: 2 wait states before the swaps)
+        asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1\n\tv_permlane16_swap_b32 %2, %3\n\t"
+                     "v_permlane16_swap_b32 %4, %5\n\tv_permlane16_swap_b32 %6, %7"
+                     : "+v"(x[0]), "+v"(y[0]), "+v"(x[1]), "+v"(y[1]), "+v"(x[2]), "+v"(y[2]),
+                       "+v"(x[3]), "+v"(y[3]));
+        const float v[8] = {x[0], x[1], x[2], x[3], y[0], y[1], y[2], y[3]};
+        // hi = f16(v), lo = f16(v - hi) (v_fma_mixlo/mixhi: one rounding each)
+        u32x4 oh, ol;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            oh[e] = gemm::x3_hi2(v[2 * e], v[2 * e + 1]);
+            ol[e] = gemm::x3_split_lo2(oh[e], v[2 * e], v[2 * e + 1]);
+            vmax = gemm::x3_absmax2(vmax, v[2 * e], v[2 * e + 1]);
+        }
+        // (the camera-concat shape too since round 5: it had kept half lines of 16 rows
+        // per instruction, nontemporal; whole lines at 3 row blocks per wave: config-3
+        // expand 6.24-6.25 vs 6.37-6.40 ms, profiles/r05_x3_expand_rb_policy_ab.txt)
+        // whole 128-byte lines per store instruction: the line of row r holds its 32
+        // hi then 32 lo channels; lanes of rows 8-15 of the 16 trade with rows 0-7 (DPP
+        // row_ror:8, written only into the bank half that takes the partner's value)
+        // so instruction A writes rows 0-7 (hi from lanes 0-7, lo from lanes 8-15) and
+        // instruction B rows 8-15 -- instead of two 64-byte halves of 16 lines (config
+        // 4, B = 65,536: 5.24-5.26 vs 5.64-5.72 ms, profiles/r04final_x3_expand_whole_lines_ab.txt)
+        u32x4 va, vb;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            va[e] = (uint32_t)__builtin_amdgcn_update_dpp((int)oh[e], (int)ol[e], 0x128, 0xF, 0xC, false);
+            vb[e] = (uint32_t)__builtin_amdgcn_update_dpp((int)ol[e], (int)oh[e], 0x128, 0xF, 0x3, false);
+        }
+        if (abl & 2) {  // (measurement builds: no output stores)
+            asm volatile("" ::"v"(va), "v"(vb));
+            continue;
+        }
+        // buffer stores through the wave's own resource (rows past M fall outside it:
+        // no exec-mask branches per store)
+        const int ra = top ? r16 : r16 - 8, rbw = top ? r16 + 8 : r16;
+        const int half = top ? 0 : 32;  // lo 64 bytes further
+        const uint32_t oa = (uint32_t)(((rb * 16 + ra) * ldy + 2 * n0 + 64 * jp + c0 + half) * 2);
+        const uint32_t ob = (uint32_t)(((rb * 16 + rbw) * ldy + 2 * n0 + 64 * jp + c0 + half) * 2);
+        __builtin_amdgcn_raw_buffer_store_b128(va, y_rsrc, oa, 0, NT ? 2 : 0);
+        __builtin_amdgcn_raw_buffer_store_b128(vb, y_rsrc, ob, 0, NT ? 2 : 0);
+    }
+}
+
+// Weight-stationary split-fp16 expand (X3, NKS <= 4, N % 512 == 0; gathered: T_out >= 16): M is
+// millions of rows and the weights are 512 KB, so the weights stay put and the rows stream (the
+// chunked kernel above stages one byte of weights into LDS per byte it stores).  Persistent, one
+// workgroup of 8 waves per CU: workgroup g owns channel group g % (N / 512) (512 channels) and
+// row stripe g / (N / 512), walking the stripe's 128-row groups s, s + S, ... (the channel groups
+// of a row are then written at about the same time by neighbouring workgroups).  Wave w owns 64
+// channels for the whole launch: its W_hi / W_lo fragments (4 k-slabs x 4 channel blocks x 2
+// u32x4 = 128 VGPRs at NKS 4) are read once, straight from global memory -- no weight ring in
+// LDS, no per-chunk barrier and drain; its scale / shift sit in LDS (4 KB per workgroup) and are
+// read per row block (32 more VGPRs held in registers: that spilled).  The 8 waves share the
+// rows: each 16-row block of a group is loaded, split into hi / lo fragments and range-checked
+// by one wave (as the chunked kernel's put()), written to LDS lane-linearly (16 B per lane and
+// fragment: 8 KB per row block at NKS 4) and read from there by all 8.  Two buffers of 8 row
+// blocks (128 KB): the next group's global loads are issued in two phases of k-slabs (16 VGPRs in
+// flight instead of 32), each under three row blocks' MFMAs, and one barrier ends a group.  The
+// output stores are never waited for inside the loop: the row loads' waits are counted past them
+// (straight-line row blocks), and the gathered form finds its windows by scalar loads.  Per row
+// block and wave the MFMA chain per accumulator and the epilogue (exp_x3_epilogue) are the
+// chunked kernel's, so the outputs are the same bits (tests/test_gpu_expand_ws.py).
+// NKS 4, gathered and plain rows: 256 VGPRs (no AGPRs), scratch 0, 132 KB of LDS: 2 waves per SIMD.
+constexpr int kWsWaves = 8;
+constexpr int kWsRows = 16 * kWsWaves;  // rows of a group: one row block prepared by each wave
+constexpr int kWsN = 64 * kWsWaves;     // channels of a workgroup
+
+template <int NKS, bool GATHER, bool NT>
+__global__ __launch_bounds__(64 * kWsWaves) void expand_gemm_x3_ws(ConvGemmParams p, GatherSrc g) {
+    constexpr int kFrag = 64 * 16;         // one fragment of a row block
+    constexpr int kBlk = 2 * NKS * kFrag;  // a row block: (hi, lo) per k-slab
+    constexpr int kBuf = kWsWaves * kBlk;
+    // the fragment buffers, then this workgroup's scale and shift (kWsN floats each)
+    __shared__ __attribute__((aligned(16))) char smem[2 * kBuf + 2 * kWsN * 4];
+
+    const int lane = threadIdx.x & 63;
+    const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int nh = p.N / kWsN;
+    const int stripe = blockIdx.x / nh, nstripes = gridDim.x / nh;
+    const int n0 = (blockIdx.x - stripe * nh) * kWsN + wid * 64;
+    const int ngroups = (p.M + kWsRows - 1) / kWsRows;
+    if (stripe >= ngroups) return;  // (the whole workgroup)
+
+    // this wave's weights: row n0 + 16 j + (l & 15), k-chunk l >> 4 of each k-slab's hi and lo
+    // halves -- the fragments the chunked kernel reads from its LDS image
+    u32x4 wh[NKS][4], wl[NKS][4];
+    {
+        const f16* wr = (const f16*)p.W + (int64_t)(n0 + (lane & 15)) * p.Kp + (lane >> 4) * 8;
+#pragma unroll
+        for (int ks = 0; ks < NKS; ++ks)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const f16* q = wr + (int64_t)(16 * j) * p.Kp + 64 * ks;
+                wh[ks][j] = *(const u32x4*)q;
+                wl[ks][j] = *(const u32x4*)(q + 32);
+            }
+    }
+    // its scale / shift through LDS (each wave its own 64 channels: no barrier), read back per row
+    // block in the epilogue's layout -- held in registers they would be 32 more VGPRs
+    float* const s_scale = (float*)(smem + 2 * kBuf) + wid * 64;
+    float* const s_shift = s_scale + kWsN;
+    s_scale[lane] = p.scale[n0 + lane];
+    s_shift[lane] = p.shift[n0 + lane];
+
+#ifdef VP3D_ABLATION
+    const int abl = g_expand_abl;  // 2 = no global stores, 16 = no MFMAs (timing only)
+#else
+    constexpr int abl = 0;
+#endif
+    // row block wid of a group: loaded as f32 (fetch), later split and written to LDS (publish), in
+    // two phases of k-slabs [0, KA) and [KA, NKS) that share 8 KA registers
+    constexpr int KA = (NKS + 1) / 2;
+    float raw[KA][8];
+    uint32_t x_hmax = 0;  // max |hi| bits of the input rows (gemm::x3_hi_bad: inf / NaN)
+    auto fetch = [&](auto phase, int grp) {
+        constexpr int KS0 = phase.value ? KA : 0, KS1 = phase.value ? NKS : KA;
+        const int mb = grp * kWsRows + wid * 16;  // (wave-uniform)
+        int m = mb + (lane & 15);
+        m = m < p.M ? m : p.M - 1;  // rows past M read a valid row; never stored
+        int64_t off = 0;
+        int len = 0, f0 = 0;
+        if constexpr (GATHER) {
+            // window b starts at sequence frame start_b - lead; row t covers window frames
+            // t*stride + tap, tap < K / lda; frame j of the window is sequence frame
+            // clamp(start_b - lead + j, 0, len - 1) ('edge' padding, generators.py:92-100).
+            // T_out >= 16 (the launcher): the block's 16 rows lie in at most two windows, located
+            // by scalar loads -- a wait for them does not wait for the wave's output stores,
+            // as one for vector loads would (vmcnt retires in order)
+            typedef const __attribute__((address_space(4))) i32x2* c_int2;  // (pairs: 8-byte aligned)
+            typedef const __attribute__((address_space(4))) int64_t* c_i64;
+            typedef const __attribute__((address_space(4))) int32_t* c_i32;
+            const int mlo = mb < p.M ? mb : p.M - 1, mhi = mb + 15 < p.M ? mb + 15 : p.M - 1;
+            const int b0 = mlo / p.T_out, b1 = mhi / p.T_out;
+            const i32x2 pr0 = ((c_int2)(const void*)g.pairs)[b0], pr1 = ((c_int2)(const void*)g.pairs)[b1];
+            const int64_t off0 = ((c_i64)(const void*)g.seq_off)[pr0.x], off1 = ((c_i64)(const void*)g.seq_off)[pr1.x];
+            const int len0 = ((c_i32)(const void*)g.seq_len)[pr0.x], len1 = ((c_i32)(const void*)g.seq_len)[pr1.x];
+            const bool second = m >= b1 * p.T_out && b1 != b0;
+            const int t = m - (second ? b1 : b0) * p.T_out;
+            off = second ? off1 : off0;
+            len = second ? len1 : len0;
+            f0 = (second ? pr1.y : pr0.y) - g.lead + t * p.stride;
+        }
+        exp_x3_load_row<NKS, KS0, KS1, GATHER>(p, g, m, off, len, f0, lane, [&](int ks, const float (&v)[8]) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) raw[ks - KS0][e] = v[e];
+        });
+    };
+    auto publish = [&](auto phase, int buf) {
+        constexpr int KS0 = phase.value ? KA : 0, KS1 = phase.value ? NKS : KA;
+        char* dst = smem + buf * kBuf + wid * kBlk + lane * 16;
+#pragma unroll
+        for (int ks = KS0; ks < KS1; ++ks) {
+            f16x8 h, l;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                float x = raw[ks - KS0][e];
+                if (ks + 1 == NKS) x = ks * 32 + (lane >> 4) * 8 + e < p.K ? x : 0.f;  // (K > 32 (NKS - 1))
+                h[e] = (f16)x;
+                l[e] = (f16)(x - (float)h[e]);
+            }
+            const u32x4 hw = __builtin_bit_cast(u32x4, h);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) x_hmax = gemm::x3_himax2(x_hmax, hw[e]);
+            *(u32x4*)(dst + (2 * ks) * kFrag) = hw;
+            *(u32x4*)(dst + (2 * ks + 1) * kFrag) = __builtin_bit_cast(u32x4, l);
+        }
+    };
+    constexpr std::integral_constant<int, 0> kPhA{};
+    constexpr std::integral_constant<int, 1> kPhB{};
+    float vmax = 0.f;  // |x| over what this wave splits (gemm::x3_range_flag)
+    __amdgpu_buffer_rsrc_t y_rsrc;
+    int cur = 0;
+    auto compute = [&](int rb) {
+        const char* ab = smem + cur * kBuf + rb * kBlk + lane * 16;
+        f32x4 acc[4];
+#pragma unroll
+        for (int ks = 0; ks < NKS; ++ks) {
+            const u32x4 ah = *(const u32x4*)(ab + (2 * ks) * kFrag);
+            const u32x4 al = *(const u32x4*)(ab + (2 * ks + 1) * kFrag);
+            if (abl & 16) {  // (measurement builds: no MFMAs; every operand stays live)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const uint32_t t = wh[ks][j][0] ^ wl[ks][j][0] ^ ah[0] ^ al[0];
+                    acc[j] = f32x4{__builtin_bit_cast(float, ks ? t ^ __builtin_bit_cast(uint32_t, acc[j][0]) : t), 0.f, 0.f, 0.f};
+                }
+                continue;
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                acc[j] = mfma16<f16>(wh[ks][j], ah, ks == 0 ? f32x4{0.f, 0.f, 0.f, 0.f} : acc[j]);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[j] = mfma16<f16>(wh[ks][j], al, acc[j]);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[j] = mfma16<f16>(wl[ks][j], ah, acc[j]);
+        }
+        int so = 4 * (lane >> 4);
+        asm volatile("" : "+v"(so));  // (read per row block: not hoisted into 32 live registers)
+        f32x2 sc[4][2], sh[4][2];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const f32x4 s4 = *(const f32x4*)&s_scale[16 * j + so];
+            const f32x4 h4 = *(const f32x4*)&s_shift[16 * j + so];
+            sc[j][0] = f32x2{s4[0], s4[1]};
+            sc[j][1] = f32x2{s4[2], s4[3]};
+            sh[j][0] = f32x2{h4[0], h4[1]};
+            sh[j][1] = f32x2{h4[2], h4[3]};
+        }
+        exp_x3_epilogue<NT>(acc, sc, sh, vmax, y_rsrc, rb, n0, p.ldy, lane, abl);
+    };
+
+    fetch(kPhA, stripe);
+    publish(kPhA, 0);
+    fetch(kPhB, stripe);
+    publish(kPhB, 0);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    for (int grp = stripe; grp < ngroups; grp += nstripes) {
+        // the next group's rows (the last trip loads its own again: no branch around the loads),
+        // each phase in flight under three row blocks' MFMAs; every wave left buffer cur ^ 1
+        // before the barrier that ended the previous group
+        const int nxt = grp + nstripes < ngroups ? grp + nstripes : grp;
+        fetch(kPhA, nxt);
+        // the group's output rows as a buffer resource (rows past M outside its range)
+        const int m0 = grp * kWsRows;
+        y_rsrc = make_rsrc((const char*)((const f16*)p.Y + (int64_t)m0 * p.ldy),
+                           clamp_range31((size_t)(p.M - m0) * p.ldy * 2));
+        // (the row blocks unrolled: straight-line code, so the waits for the fetched rows are counted
+        // past the stores issued since and sit at the publish -- in front of a loop the compiler
+        // waits for every pending load first)
+#pragma unroll
+        for (int rb = 0; rb < 3; ++rb) compute(rb);
+        publish(kPhA, cur ^ 1);
+        fetch(kPhB, nxt);
+#pragma unroll
+        for (int rb = 3; rb < 6; ++rb) compute(rb);
+        publish(kPhB, cur ^ 1);
+#pragma unroll
+        for (int rb = 6; rb < kWsWaves; ++rb) compute(rb);
+        // the published fragments written, this group's fragment reads done (the output stores stay
+        // in flight: no vmcnt wait)
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        cur ^= 1;
+    }
+    gemm::x3_range_flag(gemm::x3_hi_bad(x_hmax) ? __builtin_inff() : vmax, p.scale, p.N);
+}
+
 // resident workgroup slots per launch: two per CU (__launch_bounds__(256, 2)) for every
 // variant -- the camera-concat NKS = 5 one included since its RB 4 / 2-chunk weight ring
 // (72 KB of LDS)
@@ -590,6 +967,28 @@ hipError_t launch_t(const ConvGemmParams& p, const GatherSrc& g, int nks, hipStr
     return nt ? launch_rb_nt<CT, 4, GATHER, true, 2>(p, g, nks, s) : launch_rb_nt<CT, 4, GATHER, false, 2>(p, g, nks, s);
 }
 
+// row groups per stripe from which the weight-stationary kernel is the automatic choice: 1,024
+// windows of config 4 (5.06), the smallest batch it was measured at (0.105-0.107 vs 0.118-0.120
+// ms; 8,192 windows: 0.646 vs 0.697); smaller launches keep the chunked kernels
+constexpr int kWsMinTrips = 5;
+
+template <bool GATHER, bool NT>
+hipError_t launch_ws_nks(const ConvGemmParams& p, const GatherSrc& g, int nks, int grid, hipStream_t s) {
+    switch (nks) {
+        case 1: hipLaunchKernelGGL((expand_gemm_x3_ws<1, GATHER, NT>), dim3(grid), dim3(64 * kWsWaves), 0, s, p, g); break;
+        case 2: hipLaunchKernelGGL((expand_gemm_x3_ws<2, GATHER, NT>), dim3(grid), dim3(64 * kWsWaves), 0, s, p, g); break;
+        case 3: hipLaunchKernelGGL((expand_gemm_x3_ws<3, GATHER, NT>), dim3(grid), dim3(64 * kWsWaves), 0, s, p, g); break;
+        case 4: hipLaunchKernelGGL((expand_gemm_x3_ws<4, GATHER, NT>), dim3(grid), dim3(64 * kWsWaves), 0, s, p, g); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_ws(const ConvGemmParams& p, const GatherSrc& g, bool gather, int nks, bool nt, int grid, hipStream_t s) {
+    if (gather) return nt ? launch_ws_nks<true, true>(p, g, nks, grid, s) : launch_ws_nks<true, false>(p, g, nks, grid, s);
+    return nt ? launch_ws_nks<false, true>(p, g, nks, grid, s) : launch_ws_nks<false, false>(p, g, nks, grid, s);
+}
+
 }  // namespace
 
 bool expand_gemm_eligible(const ConvGemmParams& p, Act out_type, Act compute) {
@@ -637,6 +1036,12 @@ bool expand_gemm_x3_eligible(const ConvGemmParams& p, const GatherSrc* g) {
     return p.R == nullptr && p.M > 0;
 }
 
+// Which kernel runs (every form the same bits; VP3D_X3_EXPAND_RING picks one for measurement):
+//   * K <= 128, N % 512 == 0 and at least kWsMinTrips 128-row groups per row stripe (gathered or
+//     plain rows): the weight-stationary expand_gemm_x3_ws, one persistent workgroup per CU;
+//   * else the gathered K <= 128 shape: the chunked kernel at three workgroups per CU (RING 1, RB 2);
+//   * else (the camera concat's 5 k-slabs, plain rows): the chunked kernel at two per CU, 2-chunk
+//     weight ring, RB 3 or 2 by the rounds each leaves.
 hipError_t launch_expand_gemm_x3(const ConvGemmParams& p, const GatherSrc* g, hipStream_t stream) {
     const int nks = (p.K + 31) / 32;
     const bool nt = (int64_t)p.M * p.ldy * 2 > (int64_t)256 << 20;
@@ -659,11 +1064,22 @@ hipError_t launch_expand_gemm_x3(const ConvGemmParams& p, const GatherSrc* g, hi
         return (full + (left > 0 ? 1.0 / S : 0.0)) * rb;
     };
     const bool rb3 = cost(3) <= cost(2) + 1e-9;
-    // the gathered config-2/4 shape (K = 102, NKS 4): three workgroups per CU (RING 1, RB 2:
-    // 40 KB of LDS, 154 VGPRs) -- config 4 expand 5.18-5.21 vs 5.30-5.31 ms at B = 65,536, 0.698-0.702
-    // vs 0.703-0.705 at 8,192, same box, forwards bit-identical (profiles/r06_x3_expand_ring1_ab.txt);
-    // VP3D_X3_EXPAND_RING=2 (measurement, read at every launch) keeps the two-per-CU form below
+    // VP3D_X3_EXPAND_RING (measurement, read at every launch): unset = automatic; ws = the
+    // weight-stationary kernel wherever the shape is eligible; 1 = the three-per-CU form; 2 = the
+    // two-per-CU form.  Every form computes the same bits.
     const char* ring = getenv("VP3D_X3_EXPAND_RING");
+    const bool force_ws = ring && ring[0] == 'w' && ring[1] == 's' && !ring[2];
+    // K <= 128 (configs 2 / 4: K = 102) and whole 512-channel groups: the weight-stationary
+    // kernel (expand_gemm_x3_ws), one workgroup per CU in whole channel-group sets, gathered or
+    // plain rows.  Automatic from kWsMinTrips row groups per stripe
+    const int nh = p.N / kWsN;
+    // (gathered: windows of >= 16 rows, so that a 16-row block lies in at most two of them)
+    const int ws_grid = (nks <= 4 && p.N % kWsN == 0 && (!g || p.T_out >= 16)) ? exp_slots(1) / nh * nh : 0;
+    if (ws_grid > 0 && (force_ws || (!ring && (p.M + kWsRows - 1) / kWsRows >= (int64_t)kWsMinTrips * (ws_grid / nh))))
+        return launch_ws(p, g ? *g : none, g != nullptr, nks, nt, ws_grid, stream);
+    // otherwise the gathered config-2/4 shape (K = 102, NKS 4): three workgroups per CU (RING 1, RB 2:
+    // 40 KB of LDS, 154 VGPRs) -- config 4 expand 5.18-5.21 vs 5.30-5.31 ms at B = 65,536, 0.698-0.702
+    // vs 0.703-0.705 at 8,192, same box, forwards bit-identical (profiles/r06_x3_expand_ring1_ab.txt)
     if (!(ring && ring[0] == '2') && g && nks <= 4)
         return nt ? launch_rb_nt<f16, 2, true, true, 1, true>(p, *g, nks, stream)
                   : launch_rb_nt<f16, 2, true, false, 1, true>(p, *g, nks, stream);

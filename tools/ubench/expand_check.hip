@@ -3,11 +3,16 @@
 // on B windows, checked on sampled rows against a host fp32 sum of the 16-bit operands,
 // then timed; with the -DVP3D_ABLATION objects, per ablation (expand_gemm.hip).
 //   expand_check B RB [abl...]      (RB 0 = the library's choice)
+// VP3D_X3=1: the split-fp16 expand instead (timing only), VP3D_X3_FORMS=ws,1,2 alternating the
+// forms of VP3D_X3_EXPAND_RING (weight-stationary, three and two workgroups per CU) in every one
+// of VP3D_ROUNDS rounds; abl 2 = no stores, 16 = no MFMAs on every form.
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <algorithm>
+#include <string>
 #include <vector>
 
 #include "kernels.h"
@@ -97,21 +102,37 @@ int main(int argc, char** argv) {
         hipEvent_t e0, e1;
         (void)hipEventCreate(&e0);
         (void)hipEventCreate(&e1);
-        const int nabl = argc > 3 ? argc - 3 : 1;
-        for (int r = 0; r < 3; ++r)
-            for (int a = 0; a < nabl; ++a) {
-                const int abl = argc > 3 ? atoi(argv[3 + a]) : 0;
-                if (expand_gemm_set_ablation(abl) != hipSuccess) { printf("set ablation failed\n"); return 1; }
-                for (int i = 0; i < 2; ++i) (void)launch_expand_gemm_x3(q, &g, 0);
-                (void)hipEventRecord(e0, 0);
-                for (int i = 0; i < 10; ++i) (void)launch_expand_gemm_x3(q, &g, 0);
-                (void)hipEventRecord(e1, 0);
-                if (hipEventSynchronize(e1) != hipSuccess) { printf("launch failed\n"); return 1; }
-                float ms = 0;
-                (void)hipEventElapsedTime(&ms, e0, e1);
-                ms /= 10;
-                printf("x3 round %d abl %d: %.4f ms  %.2f TB/s output\n", r, abl, ms, (double)M * N * 4 / ms / 1e9);
+        // VP3D_X3_FORMS=ws,1,2: the forms of VP3D_X3_EXPAND_RING (expand_gemm.hip) alternating in
+        // every round of this one process; unset: the form the environment selects
+        std::vector<std::string> forms;
+        if (const char* f = getenv("VP3D_X3_FORMS")) {
+            std::string s(f);
+            for (size_t at = 0; at <= s.size();) {
+                const size_t c = std::min(s.find(',', at), s.size());
+                forms.push_back(s.substr(at, c - at));
+                at = c + 1;
             }
+        }
+        const int nforms = forms.empty() ? 1 : (int)forms.size();
+        const int nabl = argc > 3 ? argc - 3 : 1;
+        const int rounds = getenv("VP3D_ROUNDS") ? atoi(getenv("VP3D_ROUNDS")) : 3;
+        for (int r = 0; r < rounds; ++r)
+            for (int a = 0; a < nabl; ++a)
+                for (int fi = 0; fi < nforms; ++fi) {
+                    const int abl = argc > 3 ? atoi(argv[3 + a]) : 0;
+                    if (!forms.empty()) setenv("VP3D_X3_EXPAND_RING", forms[fi].c_str(), 1);
+                    if (expand_gemm_set_ablation(abl) != hipSuccess) { printf("set ablation failed\n"); return 1; }
+                    for (int i = 0; i < 2; ++i) (void)launch_expand_gemm_x3(q, &g, 0);
+                    (void)hipEventRecord(e0, 0);
+                    for (int i = 0; i < 10; ++i) (void)launch_expand_gemm_x3(q, &g, 0);
+                    (void)hipEventRecord(e1, 0);
+                    if (hipEventSynchronize(e1) != hipSuccess) { printf("launch failed\n"); return 1; }
+                    float ms = 0;
+                    (void)hipEventElapsedTime(&ms, e0, e1);
+                    ms /= 10;
+                    printf("x3 B %d form %s round %d abl %d: %.4f ms  %.2f TB/s output\n", B,
+                           forms.empty() ? "env" : forms[fi].c_str(), r, abl, ms, (double)M * N * 4 / ms / 1e9);
+                }
         return 0;
     }
     (void)expand_gemm_set_ablation(0);
