@@ -16,13 +16,14 @@ H16_TOL = {
 
 
 def make_model(strided, fw=(3, 3, 3, 3, 3), causal=False, channels=1024, jin=17, fin=2, jout=17,
-               dense=False, seed=0):
+               dense=False, seed=0, shrink_gain=0.05):
     from common.models.TemporalModel import TemporalModel, TemporalModelOptimized1f
     if strided:
         m = TemporalModelOptimized1f(jin, fin, jout, list(fw), causal=causal, channels=channels)
     else:
         m = TemporalModel(jin, fin, jout, list(fw), causal=causal, channels=channels, dense=dense)
-    sd = synth.lifter_state_dict([(k, tuple(v.shape)) for k, v in m.state_dict().items()], seed=seed)
+    sd = synth.lifter_state_dict([(k, tuple(v.shape)) for k, v in m.state_dict().items()], seed=seed,
+                                 shrink_gain=shrink_gain)
     m.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
     m.eval()
     return m, sd
