@@ -40,13 +40,15 @@ def build_parser():
     a('--by-subject', action='store_true', help='break down error by subject (on evaluation)')
     a('--export-training-curves', action='store_true', help='save training curves (not on this path)')
     # Model selection / learning (:32-38)
-    a('--use-model', dest='model_name', default='FCN', type=str, help='FCN (TemporalModel), Transformer (CoupledTransformer) or LSTM-Coupled '
-      '(CoupledLSTM; --evaluate runs the trajectory lifters over sliding windows)')
+    a('--use-model', dest='model_name', default='FCN', type=str, help='FCN (TemporalModel), Transformer (CoupledTransformer), LSTM-Coupled '
+      '(CoupledLSTM; --evaluate runs the trajectory lifters over sliding windows) or StackedPoselifter '
+      '(the MLP over the Transformer and FCN predictions; --evaluate with --transformer-weights and --fcn-weights)')
     a('-e', '--epochs', default=60, type=int, metavar='N', help='number of training epochs')
     a('-b', '--batch-size', default=1024, type=int, metavar='N', help='batch size in terms of predicted frames')
     a('-lr', '--learning-rate', default=0.001, type=float, metavar='LR', help='initial learning rate')
     a('-lrd', '--lr-decay', default=0.95, type=float, metavar='LR', help='learning rate decay per epoch')
-    # LSTM / Transformer / StackedPoseLifter (:40-63): accepted, other model families
+    # LSTM / Transformer / StackedPoseLifter (:40-63): the trajectory lifters and the ensemble of
+    # --use-model StackedPoselifter (MLP size, dropout, and the two sub-models' checkpoint paths)
     a('--hidden-features', dest='lstm_hidden_features', default=128, type=int, metavar='N')
     a('--lstm-cells', dest='lstm_cells', default=2, type=int, metavar='N')
     a('--lstm-head-architecture', dest='lstm_head_architecture', default='128,128,128', type=str, metavar='X,Y,Z')

@@ -397,4 +397,27 @@ hipError_t launch_attention(const float* QKV, int n_win, int W, int d, int heads
                             hipStream_t s);
 hipError_t launch_lstm(const LstmParams& p, hipStream_t s);
 
+// ---- StackedPoseLifter MLP, eval mode (stacked_lifter.hip, vp3d_stacked.cpp) ----
+constexpr int kStackedMaxLinear = 10;  // num_layers <= 8 hidden Linears + the first and the last
+struct StackedParams {
+    const float* ya;  // transformer prediction rows [n_rows][D]
+    const float* yb;  // FCN prediction rows [n_rows][D]
+    float* y;         // [n_rows][D]
+    const float* w;   // packed weights and biases of every Linear (offsets below, in floats)
+    int64_t n_rows;
+    int D;            // num_joints * features
+    int ld;           // LDS row pitch in floats (max padded input width + 4)
+    int n_lin;        // Linear layers
+    int Kp[kStackedMaxLinear], Np[kStackedMaxLinear];  // padded to 16
+    // Linear l: weights [Np / 16][Kp / 16][64 lanes][4] = W[16 jb + (lane & 15)][16 kt + 4 (lane >> 4) + s],
+    // zero outside (N, K); bias [Np], zero padded
+    int w_off[kStackedMaxLinear], b_off[kStackedMaxLinear];
+};
+// dynamic LDS of the 16 mi-row variant (mi = 1, 2, 4) at row pitch ld
+int stacked_mlp_lds_bytes(int mi, int ld);
+constexpr int kStackedMaxLds = 160 * 1024;  // one CU's LDS
+// once per device before the first launch: raises every variant's dynamic-LDS limit to kStackedMaxLds
+hipError_t stacked_mlp_prepare();
+hipError_t launch_stacked_mlp(const StackedParams& p, int mi, hipStream_t s);
+
 }  // namespace vp3d

@@ -4,12 +4,16 @@ branch of the reference's run.py: :290-309 model build, :400-417 device and
 checkpoint, :424-590 the training loop, :653-673 its entry, :862-995 per-action
 evaluation), and the --evaluate path of the fork's trajectory lifters
 (--use-model Transformer | LSTM-Coupled: :311-363 model build, :712-713 the
-sliding_window dispatch).
+sliding_window dispatch) and of the ensemble (--use-model StackedPoselifter: :241-288 the
+three models and their checkpoints, :714-729 the MLP on the transformer's and the FCN's
+predictions, :985-987 the two diff lines).
 
     python run.py -e 60 -c checkpoint --subjects-train S1,S2 --subjects-test S3   # train
     python run.py --evaluate synthetic --fcn-architecture 3,3,3 --subjects-test '*'
     python run.py --evaluate epoch_60.bin -c checkpoint --causal --compute-dtype bf16
     python run.py --use-model Transformer --evaluate epoch_80.bin -c checkpoint -d CMU
+    python run.py --use-model StackedPoselifter --evaluate stacked.bin -c checkpoint \
+        --transformer-weights tr.bin --fcn-weights fcn.bin
 
 Data: `-d h36m | CMU | CMU_3DPW` reads the reference's .npz layout from --data-dir
 (data_3d_<d>.npz, data_2d_<d>_<keypoints>.npz; the reference hard-codes its paths,
@@ -116,6 +120,7 @@ def group_actions(data, subjects):
 def run_evaluation(data, actions, make_generator, model_fn, metrics, action_filter=None):
     """Per-action evaluation + action-wise averages (run.py:906-987)."""
     from vp3d_amd.evaluate import camera_motion_pmcc, evaluate
+    from vp3d_amd.stacked import StackedEnsemble
     errs = {"p1": [], "p2": [], "p3": [], "vel": []}
     per_seq, infos, motion = [], [], []
     per_action = {}
@@ -139,7 +144,26 @@ def run_evaluation(data, actions, make_generator, model_fn, metrics, action_filt
     pmcc = camera_motion_pmcc(per_seq, infos, motion)
     for k, v in pmcc.items():
         print(f'PMCC (MPJPE and {k.replace("_", " ")}):', v)
-    return {"per_action": per_action, "summary": summary, "pmcc": pmcc}
+    out = {"per_action": per_action, "summary": summary, "pmcc": pmcc}
+    if isinstance(model_fn, StackedEnsemble):
+        out["ensemble_diffs"] = _ensemble_diffs(model_fn, list(per_action))
+    return out
+
+
+def _ensemble_diffs(ensemble, keys):
+    """The two diff lines of run.py:985-987 and the per-sequence values behind them.  Quirk
+    Q11, kept for drop-in output: run.py:939-940 does `fcn_diffs += fcn_diffs` on the list the
+    last evaluate() call returned, so the printed means cover the last evaluated action's
+    sequences only, and they are metres under an 'mm' label.  Every action's per-sequence
+    diffs (metres) are returned beside them."""
+    fcn = {k: list(ensemble.fcn_diffs[k]) for k in keys}
+    tr = {k: list(ensemble.transformer_diffs[k]) for k in keys}
+    printed = {"fcn": float("nan"), "transformer": float("nan")}
+    if keys:
+        printed = {"fcn": float(np.mean(fcn[keys[-1]])), "transformer": float(np.mean(tr[keys[-1]]))}
+    print('FCN Diff                        (P-MPJPE):', printed["fcn"], 'mm')
+    print('Transformer Diff                (P-MPJPE):', printed["transformer"], 'mm')
+    return {"fcn": fcn, "transformer": tr, "printed": printed}
 
 
 def _views(data, seqs):
@@ -187,6 +211,76 @@ def build_seq_model(args, J, J_out, announce=True):
             print('This model was trained for {} epochs'.format(ckpt["epoch"]))
         model.load_state_dict(ckpt["model_pos"])
     return model
+
+
+def _load_model_pos(model, path, trust, what='This model'):
+    print('Loading checkpoint', path)
+    ckpt = load_checkpoint(path, trust=trust)
+    if "epoch" in ckpt:
+        print('{} was trained for {} epochs'.format(what, ckpt["epoch"]))
+    model.load_state_dict(ckpt["model_pos"])
+
+
+def stacked_refusal(args):
+    """Why --use-model StackedPoselifter cannot run at these arguments, or None.  Checked
+    before any model is built (and before the device is looked for)."""
+    name = "--use-model StackedPoselifter"
+    if not args.evaluate:
+        return (f"{name}: training the ensemble is outside the MI355X path (the reference trains only the "
+                "MLP, over sub-models left in train mode); --evaluate runs it")
+    if args.trajectory:
+        return f"{name} takes the camera matrices through its transformer (no --trajectory)"
+    rf = int(np.prod([int(x) for x in args.fcn_architecture.split(",")]))
+    if rf != SEQ_RECEPTIVE_FIELD:
+        # run.py:242 pads every sequence for 243 frames; an FCN of another receptive field returns
+        # another number of frames than the transformer and the reference dies in a view (:720)
+        return (f"{name} needs an FCN with a receptive field of {SEQ_RECEPTIVE_FIELD} frames "
+                f"(--fcn-architecture {args.fcn_architecture} has {rf})")
+    if args.evaluate != "synthetic":
+        missing = [f for f, v in (("--transformer-weights", args.transformer_weights),
+                                  ("--fcn-weights", args.fcn_weights)) if not v]
+        if missing:
+            return f"{name} --evaluate {args.evaluate} needs " + " and ".join(missing)
+    return None
+
+
+def build_stacked_ensemble(args, J, J_out, announce=True):
+    """--use-model StackedPoselifter (reference run.py:241-288, :411-417): TemporalModel at the FCN
+    flags, CoupledTransformer at the transformer flags, StackedPoseLifter at the stacked flags.
+    Weights: --fcn-weights and --transformer-weights as given (not joined with -c), the MLP's
+    from --evaluate under -c, each 'model_pos' through the weights-only loader; with --evaluate
+    synthetic the FCN's from synth.lifter_state_dict(--seed), the other two torch's default
+    init under manual_seed(--seed).  All three in eval mode (quirk Q10); the FCN at
+    --compute-dtype, the transformer and the MLP in f32."""
+    from common.models.CamTransformer import CoupledTransformer
+    from common.models.StackedPoseLifter import StackedPoseLifter
+    from common.models.TemporalModel import TemporalModel
+    from vp3d_amd import synth
+    from vp3d_amd.stacked import StackedEnsemble
+    synthetic = args.evaluate == "synthetic"
+    if synthetic:
+        torch.manual_seed(args.seed)
+    fw = [int(x) for x in args.fcn_architecture.split(",")]
+    model_fcn = TemporalModel(J, 2, J_out, filter_widths=fw, causal=args.causal, dropout=args.fcn_dropout,
+                              channels=args.channels, dense=args.dense)
+    model_transformer = CoupledTransformer(
+        J, 2, J_out, 3, d_model=args.d_model, num_layers=args.num_layers, n_heads=args.n_heads,
+        dim_feedforward=args.dim_feedforward,
+        head_layers=[int(x) for x in args.transformer_head_architecture.split(",")], dropout=args.transformer_dropout)
+    model = StackedPoseLifter(J_out, 3, args.stacked_num_layers, args.layer_size, args.stacked_pose_lifter_dropout)
+    if announce:
+        print('INFO: Trainable parameter count:', sum(p.numel() for p in model.parameters()))
+    if synthetic:
+        sd = synth.lifter_state_dict([(k, tuple(v.shape)) for k, v in model_fcn.state_dict().items()],
+                                     seed=args.seed)
+        model_fcn.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
+    else:
+        _load_model_pos(model_transformer, args.transformer_weights, args.trust_checkpoint, 'Transformer')
+        _load_model_pos(model_fcn, args.fcn_weights, args.trust_checkpoint)
+        _load_model_pos(model, os.path.join(args.checkpoint, args.evaluate), args.trust_checkpoint)
+    model_fcn = model_fcn.cuda().eval()
+    model_fcn.set_compute_dtype(args.compute_dtype)
+    return StackedEnsemble.from_modules(model_transformer.cuda(), model_fcn, model.cuda())
 
 
 def build_model(args, J, announce=True, J_out=None):
@@ -345,10 +439,11 @@ def main(argv=None):
 
     args = parse_args(argv)
     seq_model = args.model_name in SEQ_MODELS
-    if args.model_name != "FCN" and not seq_model:
-        if args.model_name == "StackedPoselifter":
-            raise SystemExit("--use-model StackedPoselifter is outside the MI355X path (SURVEY.md §2)")
+    stacked = args.model_name == "StackedPoselifter"
+    if args.model_name != "FCN" and not seq_model and not stacked:
         raise KeyError('Invalid model name')  # run.py:392-393
+    if stacked and stacked_refusal(args):
+        raise SystemExit(stacked_refusal(args))
     if not torch.cuda.is_available():
         raise SystemExit("run.py evaluates on the MI355X (no CPU fallback)")
     if seq_model and not args.evaluate:
@@ -366,9 +461,12 @@ def main(argv=None):
     data = load_data(args)
     subjects = list(data.keys()) if args.subjects_test in (None, "*") else args.subjects_test.split(",")
     j2, j3 = joint_counts(data)
-    model = build_model(args, j2, J_out=j3).cuda().eval()
-    if seq_model:
-        receptive_field = SEQ_RECEPTIVE_FIELD
+    if stacked:
+        model = build_stacked_ensemble(args, j2, j3)
+    else:
+        model = build_model(args, j2, J_out=j3).cuda().eval()
+    if seq_model or stacked:
+        receptive_field = SEQ_RECEPTIVE_FIELD  # run.py:242 for the ensemble
     else:
         model.set_compute_dtype(args.compute_dtype)
         receptive_field = model.receptive_field()

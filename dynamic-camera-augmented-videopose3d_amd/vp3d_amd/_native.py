@@ -58,6 +58,7 @@ EXPORTS = [
     "vp3d_train_dropout_mask", "vp3d_train_relu_mask", "vp3d_train_layer_rows", "vp3d_adam_step", "vp3d_mpjpe_backward",
     "vp3d_seq_weight_count", "vp3d_seq_create", "vp3d_seq_destroy", "vp3d_seq_forward",
     "vp3d_seq_sliding_window",
+    "vp3d_stacked_weight_count", "vp3d_stacked_create", "vp3d_stacked_forward", "vp3d_stacked_destroy",
 ]
 
 
@@ -96,6 +97,19 @@ class vp3d_seq_cfg(ctypes.Structure):
         ("head_layers", ctypes.c_int32 * SEQ_MAX_HEAD),
         ("max_len", ctypes.c_int32),
         ("eps", ctypes.c_float),
+    ]
+
+
+STACKED_MAX_LAYERS = 8
+STACKED_MAX_LAYER_SIZE = 512
+
+
+class vp3d_stacked_cfg(ctypes.Structure):
+    _fields_ = [
+        ("num_joints", ctypes.c_int32),
+        ("features", ctypes.c_int32),
+        ("num_layers", ctypes.c_int32),
+        ("layer_size", ctypes.c_int32),
     ]
 
 
@@ -168,6 +182,11 @@ _SIGNATURES = {
     "vp3d_seq_destroy": (_int, [_vp]),
     "vp3d_seq_forward": (_int, [_vp, _vp, _vp, _int, _int, _vp, _vp]),
     "vp3d_seq_sliding_window": (_int, [_vp, _vp, _vp, _int, _int, _vp, _vp]),
+    "vp3d_stacked_weight_count": (_int, [ctypes.POINTER(vp3d_stacked_cfg)]),
+    "vp3d_stacked_create": (_int, [ctypes.POINTER(vp3d_stacked_cfg), ctypes.POINTER(_vp), _int,
+                                   ctypes.POINTER(_vp)]),
+    "vp3d_stacked_forward": (_int, [_vp, _vp, _vp, _i64, _vp, _vp]),
+    "vp3d_stacked_destroy": (_int, [_vp]),
     "vp3d_last_error": (ctypes.c_char_p, []),
     "vp3d_abi_version": (_int, []),
     "vp3d_build_hash": (ctypes.c_char_p, []),

@@ -1,8 +1,9 @@
 """Evaluation harness of the FCN path (the part of reference run.py the hot path serves).
 
 Restates run.py:677-774 (`evaluate`) and :906-983 (`run_evaluation`) for the
-temporal lifter and the trajectory lifters: per action, an UnchunkedGenerator over
-that action's sequences, one model call per sequence (run.py:710-713), Protocol #1 MPJPE accumulated with the
+temporal lifter, the trajectory lifters and the stacked ensemble: per action, an
+UnchunkedGenerator over that action's sequences, one model call per sequence
+(run.py:710-720), Protocol #1 MPJPE accumulated with the
 reference's N-weighting (run.py:734-738, x1000 -> mm at :762), plus the
 post-path protocols (P-MPJPE :744-747, N-MPJPE :732, MPJVE :750) and the PMCC of
 per-sequence error vs camera motion (:946-983).
@@ -55,25 +56,39 @@ def _is_seq_lifter(model) -> bool:
     return isinstance(model, (CamLSTMBase, CamTransformerBase))
 
 
+def _is_ensemble(model) -> bool:
+    from .stacked import StackedEnsemble
+    return isinstance(model, StackedEnsemble)
+
+
 def evaluate(generator, model: Callable, metrics, action: str | None = None, verbose: bool = True):
     """One pass over `generator` -- an UnchunkedGenerator, or any iterable of
     (cams, batch_3d, batch_2d, info) with a leading batch axis of 1.  The model call
-    follows run.py:710-713: a temporal lifter sees the padded 2D sequence, a trajectory
+    follows run.py:710-720: a temporal lifter sees the padded 2D sequence, a trajectory
     lifter (CamLSTMBase / CamTransformerBase) runs sliding_window(inputs_2d, inputs_cam,
-    generator.seq_length).  Returns (e1, e2, e3, ev) in mm and per-sequence e1."""
+    generator.seq_length), a StackedEnsemble runs both and the MLP on the two predictions
+    and records the per-sequence P-MPJPE differences on itself (run.py:722-729).  Returns
+    (e1, e2, e3, ev) in mm and per-sequence e1."""
     e1 = e2 = e3 = ev = 0.0
     N = 0
     per_seq: List[float] = []
     infos: List[dict] = []
     motion: List[float] = []
-    seq_lifter = _is_seq_lifter(model)
+    ensemble = _is_ensemble(model)
+    seq_lifter = not ensemble and _is_seq_lifter(model)
     seq_length = getattr(generator, "seq_length", None)
-    if seq_lifter and seq_length is None:
+    if (seq_lifter or ensemble) and seq_length is None:
         raise ValueError("a trajectory lifter needs the generator's seq_length (run.py:713)")
+    if ensemble:
+        model.begin_action(action)
     batches = generator.next_epoch() if hasattr(generator, "next_epoch") else generator
     with torch.no_grad():
         for cams, batch_3d, batch_2d, info in batches:
-            if seq_lifter:
+            if ensemble:
+                pred_t, pred_f, pred = model.predict(batch_2d, cams, seq_length)
+                pred = pred.view(batch_3d.shape)  # run.py:720
+                model.record(metrics, pred_t, pred_f, pred)
+            elif seq_lifter:
                 pred = model.sliding_window(batch_2d, cams, seq_length)
             else:
                 pred = model(batch_2d)

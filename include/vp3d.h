@@ -355,6 +355,37 @@ int vp3d_seq_forward(vp3d_seq_lifter* h, const float* x2d, const float* xcam, in
 int vp3d_seq_sliding_window(vp3d_seq_lifter* h, const float* x2d, const float* xcam, int L, int window, float* y,
                             void* stream);
 
+/* ---- stacked pose lifter: the ensemble MLP, eval mode ----
+ * StackedPoseLifter (common/models/StackedPoseLifter.py:4-56; built at run.py:241-288, called
+ * per sequence at run.py:719-720): Linear(2 J F -> layer_size), ReLU, Dropout, num_layers x
+ * [Linear(layer_size -> layer_size), ReLU, Dropout], Linear(layer_size -> J F) on rows of
+ * [transformer prediction | FCN prediction] (:46-49).  One kernel launch, exact f32. */
+#define VP3D_STACKED_MAX_LAYERS 8
+#define VP3D_STACKED_MAX_LAYER_SIZE 512
+#define VP3D_STACKED_MAX_POSE 512 /* num_joints * features */
+
+typedef struct vp3d_stacked_cfg {
+    int32_t num_joints, features; /* StackedPoseLifter.py:16-17                             */
+    int32_t num_layers;           /* hidden Linear(layer_size, layer_size) layers (:27-30), 0..8 */
+    int32_t layer_size;           /* :20, 1..512                                            */
+} vp3d_stacked_cfg;
+
+typedef struct vp3d_stacked vp3d_stacked;
+
+/* Host weight arrays vp3d_stacked_create expects: the state_dict order of the mlp_layers
+ * ModuleList (StackedPoseLifter.py:22-34), mlp_layers.{0, 3, 6, ...}.{weight, bias}:
+ * 2 * (num_layers + 2) arrays.  Returns the count, or -1 for an invalid configuration. */
+int vp3d_stacked_weight_count(const vp3d_stacked_cfg* cfg);
+/* Validates the configuration first (VP3D_ERR_ASSERT and a message naming the limit, before
+ * any device call), then packs the weights into one device buffer in the kernel's operand order. */
+int vp3d_stacked_create(const vp3d_stacked_cfg* cfg, const float* const* weights, int n_weights, vp3d_stacked** out);
+/* forward(input_3d_transformer, input_3d_FCN) (StackedPoseLifter.py:37-56): y_transformer and
+ * y_fcn device f32 (n_rows, J * F), contiguous -> out device f32 (n_rows, J * F).  A row's
+ * result depends on that row alone (not on n_rows or its position), bit for bit. */
+int vp3d_stacked_forward(vp3d_stacked* h, const float* y_transformer, const float* y_fcn, int64_t n_rows, float* out,
+                         void* stream);
+int vp3d_stacked_destroy(vp3d_stacked* h);
+
 /* ---- on-device input path (common/camera.py, common/generators.py) ---- */
 
 /* normalize_screen_coordinates (camera.py:14-18): out = X/w*2 - [1, h/w] for
