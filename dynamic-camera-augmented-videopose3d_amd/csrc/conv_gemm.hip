@@ -247,7 +247,10 @@ __global__ __launch_bounds__(256) void conv_gemm_f32(ConvGemmParams p) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    const int nk = p.Kp / BK;
+    // K steps up to K, not Kp: the weight columns past K are zero, but A_VEC does not guard
+    // k < K, and with K % 16 == 0 < Kp (a 96-wide Linear: Kp = 128) a step past K would read
+    // the following rows -- past the end of the A buffer at the last row
+    const int nk = (p.K + BK - 1) / BK;
     gload(0);
     lstore(0);
     __syncthreads();

@@ -559,7 +559,10 @@ hipError_t launch_attention(const float* QKV, int n_win, int W, int d, int heads
             hipLaunchKernelGGL(attention_last_kernel<32>, dim3(n_win), dim3(64 * heads), 0, s, QKV, W, d, scale, O);
         return hipGetLastError();
     }
-    if (!last_only && W <= ATT_WMAX && (dh == 16 || dh == 32)) {
+    // the MFMA kernel moves K, V and O rows as 16-byte pieces (vp3d_seq.cpp carves its workspace
+    // on 16-byte boundaries; d and dh are multiples of 4); anything else goes to the scalar kernel
+    const auto a16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+    if (!last_only && W <= ATT_WMAX && (dh == 16 || dh == 32) && d % 4 == 0 && a16(QKV) && a16(O)) {
         if (dh == 16)
             hipLaunchKernelGGL(attention_mfma_kernel<16>, grid, dim3(256), 0, s, QKV, W, d, scale, O);
         else

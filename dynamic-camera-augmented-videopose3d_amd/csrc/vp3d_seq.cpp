@@ -150,10 +150,13 @@ int validate(const vp3d_seq_cfg* c) {
         const int dh = c->d_model / c->n_heads;
         if (dh != 16 && dh != 32 && dh != 64) return fail(VP3D_ERR_ARG, "head dim must be 16, 32 or 64");
         if (c->max_len < 1) return fail(VP3D_ERR_ARG, "max_len (positional-encoding rows) must be positive");
+        if (c->dim_feedforward < 1) return fail(VP3D_ERR_ARG, "dim_feedforward must be positive");
     } else {
         if (c->d_model != 64 && c->d_model != 128) return fail(VP3D_ERR_ARG, "LSTM hidden size must be 64 or 128");
         if (c->num_layers > 4) return fail(VP3D_ERR_ARG, "at most 4 LSTM cells");
     }
+    for (int j = 0; j < c->n_head_layers; ++j)
+        if (c->head_layers[j] < 1) return fail(VP3D_ERR_ARG, "head layer widths must be positive");
     return VP3D_OK;
 }
 
@@ -277,20 +280,30 @@ int run(vp3d_seq_lifter* h, const float* x2d, const float* xcam, int64_t n_frame
     const int d = c.d_model;
     const int64_t rows = (int64_t)n_win * W;
     if (rows > (int64_t)1 << 31 || n_frames > (int64_t)1 << 31) return fail(VP3D_ERR_ARG, "too many rows");
+    // every buffer in front of the head's starts on a 16-byte boundary (r4): a frame row is
+    // 46 floats, so with an odd frame count everything carved behind X would otherwise sit
+    // on 8-byte boundaries, under the 16-byte accesses of the attention kernels
+    const auto r4 = [](size_t n) { return (n + 3) & ~(size_t)3; };
     size_t need;
     const int hmax = *std::max_element(c.head_layers, c.head_layers + c.n_head_layers);
     if (c.kind == VP3D_SEQ_TRANSFORMER) {
         if (W > c.max_len) return fail(VP3D_ERR_ASSERT, "window longer than the positional encoding");
+        // attention holds K and V of one (window, head) in 64 KiB of LDS (launch_attention)
+        const int dh = d / c.n_heads, wmax = 64 * 1024 / (2 * dh * (int)sizeof(float));
+        if (W > wmax)
+            return fail(VP3D_ERR_ARG, "window of " + std::to_string(W) + " frames with head dim " + std::to_string(dh) +
+                                          ": the attention kernels take at most " + std::to_string(wmax) +
+                                          " frames at this head dim (8192 / head dim)");
         const int ff = c.dim_feedforward;
-        need = (size_t)n_frames * cin + (size_t)n_frames * d + (size_t)rows * (3 * d + 3 * d + std::max(ff, d)) +
-               (size_t)n_win * 2 * std::max(hmax, d);
+        need = r4((size_t)n_frames * cin) + (size_t)n_frames * d + (size_t)rows * (3 * d + 3 * d) +
+               r4((size_t)rows * std::max(ff, d)) + (size_t)n_win * 2 * std::max(hmax, d);
     } else {
-        need = (size_t)n_frames * cin + (size_t)n_frames * 4 * d + (size_t)n_win * 2 * std::max(hmax, d);
+        need = r4((size_t)n_frames * cin) + (size_t)n_frames * 4 * d + (size_t)n_win * 2 * std::max(hmax, d);
     }
     int rc = ensure_ws(h, need);
     if (rc) return rc;
     float* X = h->ws;
-    float* cur = X + (size_t)n_frames * cin;
+    float* cur = X + r4((size_t)n_frames * cin);
     HIP_TRY(launch_concat_frames(x2d, f2, xcam, 12, n_frames, X, s));
     const int mx = std::max(hmax, d);
     float* hv;  // (n_win x d) input of the head, = bufs[1]
@@ -302,7 +315,7 @@ int run(vp3d_seq_lifter* h, const float* x2d, const float* xcam, int64_t n_frame
         float* O = QKV + (size_t)rows * 3 * d;         // rows x d
         float* T1 = O + (size_t)rows * d;              // rows x d
         float* F1 = T1 + (size_t)rows * d;             // rows x max(ff, d)
-        hx = F1 + (size_t)rows * std::max(c.dim_feedforward, d);
+        hx = F1 + r4((size_t)rows * std::max(c.dim_feedforward, d));
         HIP_TRY(run_linear(h->in_proj, X, (int)n_frames, P, s));
         HIP_TRY(launch_layernorm_rows(P, d, rows, W, win_stride, h->pe, h->pre_g, h->pre_b, c.eps, Hb, s));
         for (int l = 0; l < c.num_layers; ++l) {
