@@ -101,6 +101,9 @@ def build_parser():
            '(the reference hard-codes /vol/bitbucket/bw1222/data/npz)')
     a('--compute-dtype', default='fp32', choices=['fp32', 'f16x3', 'bf16', 'fp16'],
       help='arithmetic of the conv stack (fp32 = parity path; f16x3 = split fp16, fp32-level results on the 16-bit MFMAs)')
+    a('--x3-calibrate', default=0, type=int, metavar='N',
+      help='with --evaluate and --compute-dtype f16x3: choose the exact power-of-two activation pre-scale '
+           'of the f16x3 path on the first N frames of the first evaluated sequence (0 = off)')
     a('--trust-checkpoint', action='store_true',
       help='allow full unpickling of a checkpoint you created yourself (by default only tensors, '
            'plain containers and the numpy RandomState of a run.py checkpoint are admitted)')

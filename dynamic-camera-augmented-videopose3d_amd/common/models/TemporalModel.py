@@ -93,6 +93,7 @@ class TemporalModelBase(nn.Module):
         self._lifter = None
         self._lifter_key = None
         self._trainer = None
+        self._x3_prescale = None  # f16x3 activation pre-scale exponents (set_f16x3_prescale)
 
     def _build_stack(self, strided, dense):
         pad, shift, blocks = _plan_blocks(self.filter_widths, self.causal, strided, dense)
@@ -166,8 +167,52 @@ class TemporalModelBase(nn.Module):
                                         self.filter_widths, self.causal, self.channels,
                                         self.dense, self._variant, state, device=device,
                                         bn_eps=self.expand_bn.eps)
+            if self._x3_prescale is not None:
+                self._lifter.set_x3_prescale(self._x3_prescale)
         self._lifter_key = key
         return self._lifter
+
+    # ---- f16x3 activation pre-scale (opt-in) ----------------------------------------
+    def set_f16x3_prescale(self, p):
+        """One power-of-two exponent per conv layer output (the expand, then each block's k-conv
+        and 1x1; the shrink has none): the f16x3 path then stores layer l's activations times
+        2^p[l], exactly, which lifts small activations off the split's f16 subnormal floor
+        (DESIGN.md §2).  The expand and every block's 1x1 output share one exponent (the residual
+        add joins them).  None or all zeros clears it.  A plain attribute, not a buffer (the
+        state_dict keys stay the reference's); re-applied whenever the native handle is rebuilt
+        or reloaded.  The other compute dtypes are untouched."""
+        from vp3d_amd.x3_prescale import check_prescale
+        p = None if p is None else check_prescale(p, self.filter_widths)
+        if p is not None and not any(p):
+            p = None
+        self._x3_prescale = p
+        if self._lifter is not None:
+            self._lifter.set_x3_prescale(p)
+        return self
+
+    def f16x3_prescale(self):
+        """The exponents set_f16x3_prescale / calibrate_f16x3 left (all zeros when none are set)."""
+        from vp3d_amd.x3_prescale import n_prescale_layers
+        return list(self._x3_prescale) if self._x3_prescale is not None else [0] * n_prescale_layers(self.filter_widths)
+
+    def calibrate_f16x3(self, x, headroom_bits=6):
+        """Choose and set the f16x3 pre-scale from one calibration batch x (B, T, J_in, F): the fp32
+        forward runs layer by layer, a device reduction takes each layer's absmax / rms / share
+        of values under 2^-3, and vp3d_amd.x3_prescale.choose_prescale picks the exponents that
+        leave `headroom_bits` bits under the f16 range.  Returns (exponents, stats).  Eval mode
+        and a HIP tensor only."""
+        from vp3d_amd.x3_prescale import choose_prescale
+        if self.training:
+            raise RuntimeError("vp3d: calibrate_f16x3 needs eval mode (model.eval()): it measures the eval-mode "
+                               "activations the f16x3 path stores")
+        if not x.is_cuda:
+            raise RuntimeError("vp3d: calibrate_f16x3 runs on the MI355X kernels only (no CPU fallback); "
+                               "pass x.cuda()")
+        assert len(x.shape) == 4 and x.shape[-2] == self.num_joints_in and x.shape[-1] == self.in_features
+        stats = self.native_lifter(x.device).calibrate_x3(x)
+        p = choose_prescale(stats, self.filter_widths, headroom_bits)
+        self.set_f16x3_prescale(p)
+        return p, stats
 
     def sync_status(self):
         """Synchronise and raise RuntimeError if an eval-mode forward of this module reported a

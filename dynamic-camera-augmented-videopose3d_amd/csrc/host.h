@@ -80,6 +80,17 @@ struct Layer {
     // [Np][2 Kp] with each 32-wide K group stored [hi(32) | lo(32)]; scale_x3 = scale * 2^-e
     uint16_t* wx3 = nullptr;
     float* scale_x3 = nullptr;
+    // the f16x3 path's own shift (vp3d_set_x3_prescale): shift * 2^p_out, a copy of `shift` while
+    // no pre-scale is set; `shift` itself is shared with the fp32 / bf16 / fp16 paths
+    float* shift_x3 = nullptr;
+    // shrink only: the scale 2^-p_chain of the f16x3 forward's exact-f32 shrink over f32 rows
+    // (VP3D_X3_SHRINK=f32, cout > 64); all ones while no pre-scale is set
+    float* scale_x3_f32 = nullptr;
+    // host copies of what the f16x3 vectors are folded from (fold_x3 in vp3d_capi.cpp): the
+    // folded BN (scale, shift), the weights' power of two and the sign balancing
+    std::vector<float> sc_host, sh_host;
+    int e_x3 = 0;
+    bool balance_x3 = true;
 };
 
 struct ProfEvent {
@@ -115,6 +126,11 @@ struct vp3d_handle {
     // first forward whose plan splits a layer; flags zeroed then, each owner unit takes its
     // helpers' counts back out (and vp3d_sync_status re-zeroes them after a reported timeout)
     void* sk_ws = nullptr;
+    // f16x3 activation pre-scale (vp3d_set_x3_prescale): layer l's stored split rows hold
+    // a * 2^x3_prescale[l]; one exponent per conv layer output (the shrink has none), all zero
+    // by default.  x3_stats: the calibration pass's per-layer device accumulators
+    std::vector<int> x3_prescale;
+    vp3d::ActStats* x3_stats = nullptr;
     // host-mapped fault word (vp3d::kFault* bits): a split-K owner unit whose helpers did not
     // arrive in time, a non-finite f16x3 output; checked at the next call and by vp3d_sync_status
     unsigned* sk_err_host = nullptr;

@@ -325,6 +325,25 @@ constexpr unsigned kFaultNonFinite = 2u;
 hipError_t launch_pose_metrics(const float* pred, const float* target, int64_t n_frames, int J, double* acc,
                                hipStream_t s);
 
+// act_stats.hip: the f16x3 calibration pass (vp3d_x3_calibrate) reduces one layer's f32 output
+// rows a[0, n) into `out` (zeroed by the caller, accumulated with atomics):
+//   absmax_bits  max over |a| of its f32 bit pattern (an unsigned max: orders like the value,
+//                +inf above every finite one and a NaN above +inf, so a non-finite value shows)
+//   sumsq        sum of a^2 in f64
+//   small        count of a != 0 with |a| < 2^-3: the values whose split-fp16 `lo` half is an
+//                f16 subnormal
+// `out` is kActStatSlots accumulators, one 128-byte line each: workgroup w adds into slot
+// w % kActStatSlots (atomics of thousands of workgroups on one address serialise), the host
+// combines the slots.
+struct alignas(128) ActStats {
+    unsigned absmax_bits;
+    unsigned pad_;
+    double sumsq;
+    unsigned long long small;
+};
+constexpr int kActStatSlots = 64;
+hipError_t launch_act_stats(const float* a, int64_t n, ActStats* out, hipStream_t s);
+
 // ---- training step (train.hip, vp3d_train.cpp) ----
 // weight gradient of one conv: part[s][n][k] over row splits s (TN GEMM over rows)
 struct WgradParams {

@@ -169,6 +169,9 @@ void free_layers(vp3d_handle* h) {
         hipFree(L.wfh);
         hipFree(L.wx3);
         hipFree(L.scale_x3);
+        hipFree(L.shift_x3);
+        hipFree(L.scale_x3_f32);
+        L.shift_x3 = L.scale_x3_f32 = nullptr;
         L.w32 = nullptr;
         L.wbf = L.wh = nullptr;
         L.scale = L.shift = nullptr;
@@ -176,6 +179,48 @@ void free_layers(vp3d_handle* h) {
         L.wx3 = nullptr;
         L.scale_x3 = nullptr;
     }
+}
+
+// The f16x3 path's epilogue vectors of every layer, folded from the host copies upload_weights
+// keeps (Layer::sc_host / sh_host / e_x3) and the handle's activation pre-scale
+// (vp3d_set_x3_prescale): layer l's stored split rows hold a * 2^p[l], so a producing layer
+// undoes its weights' 2^e and its input's 2^p_in and applies its own 2^p_out,
+//   scale_x3 = +-scale * 2^(-e - p_in + p_out),  shift_x3 = shift * 2^p_out
+// (p_in = 0 for the expand: raw f32 rows; the residual a 1x1 adds is stored at the chain's
+// exponent, which is that layer's p_out).  The shrink has p_out = 0: it absorbs the chain's
+// inverse and keeps its bias; scale_x3_f32 is the same inverse for its exact-f32 form.  Powers
+// of two only: with every exponent zero these are the bits of the unscaled fold.
+int fold_x3(vp3d_handle* h) {
+    const int nl = (int)h->layers.size();
+    for (int li = 0; li < nl; ++li) {
+        Layer& L = h->layers[li];
+        const bool is_shrink = li == nl - 1;
+        const int p_in = li == 0 ? 0 : h->x3_prescale[li - 1];
+        const int p_out = is_shrink ? 0 : h->x3_prescale[li];
+        // [cout scales | the fault word's device address] (gemm::x3_range_flag; the kernels
+        // run with cout % 64 == 0, so the address is 8-byte aligned at index cout).  The
+        // shrink (cout = 51): scales padded with zeros to 64 channels (its split GEMM runs
+        // 64 columns, the W rows past cout are zero), no range guard (f32 poses out)
+        const int tail = is_shrink ? (L.cout + 63) / 64 * 64 : (L.cout + 1) & ~1;
+        std::vector<float> scx3(tail + 2, 0.f), shx3(tail, 0.f);
+        for (int o = 0; o < L.cout; ++o) {
+            scx3[o] = std::ldexp(L.balance_x3 && (o & 1) ? -L.sc_host[o] : L.sc_host[o], -L.e_x3 - p_in + p_out);
+            shx3[o] = std::ldexp(L.sh_host[o], p_out);
+        }
+        static_assert(sizeof(unsigned*) == 2 * sizeof(float), "pointer = two floats");
+        std::memcpy(&scx3[tail], &h->sk_err_dev, sizeof(unsigned*));
+        if (!L.scale_x3) HIP_TRY(hipMalloc(&L.scale_x3, scx3.size() * 4));
+        if (!L.shift_x3) HIP_TRY(hipMalloc(&L.shift_x3, shx3.size() * 4));
+        HIP_TRY(hipMemcpy(L.scale_x3, scx3.data(), scx3.size() * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(L.shift_x3, shx3.data(), shx3.size() * 4, hipMemcpyHostToDevice));
+        if (is_shrink) {
+            std::vector<float> s32(L.cout);
+            for (int o = 0; o < L.cout; ++o) s32[o] = std::ldexp(L.sc_host[o], -p_in);
+            if (!L.scale_x3_f32) HIP_TRY(hipMalloc(&L.scale_x3_f32, s32.size() * 4));
+            HIP_TRY(hipMemcpy(L.scale_x3_f32, s32.data(), s32.size() * 4, hipMemcpyHostToDevice));
+        }
+    }
+    return VP3D_OK;
 }
 
 int upload_weights(vp3d_handle* h, const float* const* w, int n) {
@@ -282,24 +327,16 @@ int upload_weights(vp3d_handle* h, const float* const* w, int n) {
                     px3[q] = hi;
                     px3[q + 32] = f32_to_f16_rne(v - f16_to_f32(hi));
                 }
-            // [cout scales | the fault word's device address] (gemm::x3_range_flag; the kernels
-            // run with cout % 64 == 0, so the address is 8-byte aligned at index cout).  The
-            // shrink (cout = 51): scales padded with zeros to 64 channels (its split GEMM runs
-            // 64 columns, the W rows past cout are zero), no range guard (f32 poses out)
-            const int tail = is_shrink ? (L.cout + 63) / 64 * 64 : (L.cout + 1) & ~1;
-            std::vector<float> scx3(tail + 2, 0.f);
-            for (int o = 0; o < L.cout; ++o) scx3[o] = std::ldexp(balance && (o & 1) ? -sc[o] : sc[o], -e);
-            static_assert(sizeof(unsigned*) == 2 * sizeof(float), "pointer = two floats");
-            std::memcpy(&scx3[tail], &h->sk_err_dev, sizeof(unsigned*));
-            if (!L.wx3) {
-                HIP_TRY(hipMalloc(&L.wx3, px3.size() * 2));
-                HIP_TRY(hipMalloc(&L.scale_x3, scx3.size() * 4));
-            }
+            if (!L.wx3) HIP_TRY(hipMalloc(&L.wx3, px3.size() * 2));
             HIP_TRY(hipMemcpy(L.wx3, px3.data(), px3.size() * 2, hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(L.scale_x3, scx3.data(), scx3.size() * 4, hipMemcpyHostToDevice));
+            // the epilogue vectors (scale_x3, shift_x3) are folded from these by fold_x3
+            L.sc_host = sc;
+            L.sh_host = shv;
+            L.e_x3 = e;
+            L.balance_x3 = balance;
         }
     }
-    return VP3D_OK;
+    return fold_x3(h);
 }
 
 // Temporal length after each layer for an input of T frames; returns false if
@@ -445,7 +482,8 @@ constexpr const char* kSplitFaultMsg =
     "handle produced wrong poses); vp3d_sync_status clears the fault";
 constexpr const char* kNonFiniteMsg =
     "f16x3: an earlier forward on this handle split an activation past the f16 range (|x| <= "
-    "65504) or produced non-finite poses; its outputs are not valid -- run those inputs in fp32. "
+    "65504) or produced non-finite poses; its outputs are not valid -- run those inputs in fp32 "
+    "(with an activation pre-scale set: re-calibrate with more headroom or clear the pre-scale). "
     "vp3d_sync_status clears the fault";
 const char* fault_msg(unsigned w) { return (w & vp3d::kFaultSplitTimeout) ? kSplitFaultMsg : kNonFiniteMsg; }
 
@@ -483,6 +521,7 @@ int vp3d_create(const vp3d_cfg* cfg, const float* const* weights, int n_weights,
     if (h->cfg.bn_eps <= 0.f) h->cfg.bn_eps = 1e-5f;
     hipGetDevice(&h->device);
     build_geometry(h);
+    h->x3_prescale.assign(h->layers.size() - 1, 0);
     // the device fault word (vp3d_sync_status), host-mapped; before the weights: the f16x3
     // layers keep its address after their scale_x3 vectors
     rc = ensure_fault_word(h);
@@ -515,6 +554,7 @@ int vp3d_destroy(vp3d_handle* h) {
     if (h->ws) hipFree(h->ws);
     if (h->gather_ws) hipFree(h->gather_ws);
     if (h->sk_ws) hipFree(h->sk_ws);
+    if (h->x3_stats) hipFree(h->x3_stats);
     if (h->sk_err_host) hipHostFree(h->sk_err_host);
     for (auto& e : h->pending) {
         hipEventDestroy(e.a);
@@ -565,8 +605,10 @@ int vp3d_reserve(vp3d_handle* h, int B, int T, int dtype) {
 
 // The forward of B windows of T frames.  x: (B, T, J_in*F) f32, or nullptr with `gs`
 // describing where the windows are gathered from (vp3d_forward_windows).
+// `calib` (fp32 only): per-layer device accumulators of the calibration pass; every conv
+// layer's f32 output rows (not the shrink's poses) are reduced into calib[layer] after its launch.
 static int forward_impl(vp3d_handle* h, const float* x, int B, int T, float* y, int dtype, void* stream,
-                        const GatherSrc* gs) {
+                        const GatherSrc* gs, vp3d::ActStats* calib = nullptr) {
     int dev = 0;
     hipGetDevice(&dev);
     if (dev != h->device) return fail(VP3D_ERR_STATE, "handle belongs to another device");
@@ -611,7 +653,8 @@ static int forward_impl(vp3d_handle* h, const float* x, int B, int T, float* y, 
         ConvGemmParams p{};
         p.A = cur_in;
         p.scale = L.scale;
-        p.shift = L.shift;
+        // f16x3: the shift at the layer's pre-scale (fold_x3); L.shift stays the other paths'
+        p.shift = dtype == VP3D_DTYPE_F16X3 ? L.shift_x3 : L.shift;
         p.M = B * len[li];
         p.N = L.cout;
         p.K = L.K;
@@ -673,8 +716,10 @@ static int forward_impl(vp3d_handle* h, const float* x, int B, int T, float* y, 
             e = launch_conv_gemm_x3_shrink(p, s);
             launched = true;
         } else if (x3 && last) {
-            // shrink: the exact f32 GEMM over the f32 rows the layer before wrote
+            // shrink: the exact f32 GEMM over the f32 rows the layer before wrote (rows at the
+            // chain's pre-scale: undone by this form's own scale vector, ones without one)
             p.W = L.w32;
+            p.scale = L.scale_x3_f32;
             e = launch_conv_gemm(p, Act::F32, Act::F32, Act::F32, s);
             launched = true;
         } else if (x3 && first && nl > 2 && [&] {
@@ -790,6 +835,10 @@ static int forward_impl(vp3d_handle* h, const float* x, int B, int T, float* y, 
             hipEventRecord(pe.b, s);
             h->pending.push_back(pe);
         }
+        if (calib && !last) {
+            const hipError_t ce = launch_act_stats((const float*)p.Y, (int64_t)p.M * L.cout, calib + (size_t)li * vp3d::kActStatSlots, s);
+            if (ce != hipSuccess) return fail(VP3D_ERR_HIP, std::string("activation statistics: ") + hipGetErrorString(ce));
+        }
         // the k-conv of a block reads the block input; remember it for the 1x1's residual
         if (!last && !L.residual && !first) {
             block_in = cur_in;
@@ -857,6 +906,122 @@ int vp3d_sync_status(vp3d_handle* h, void* stream) {
     }
     *(volatile unsigned*)h->sk_err_host = 0u;
     return fail(VP3D_ERR_STATE, fault_msg(w));
+}
+
+int vp3d_set_x3_prescale(vp3d_handle* h, const int32_t* p, int n) {
+    if (!h) return fail(VP3D_ERR_ARG, "handle is NULL");
+    if (!p) return fail(VP3D_ERR_ARG, "exponents is NULL");
+    const int want = (int)h->layers.size() - 1;
+    if (n != want)
+        return fail(VP3D_ERR_ARG, "f16x3 pre-scale: expected " + std::to_string(want) +
+                                      " exponents (one per conv layer output, none for the shrink), got " +
+                                      std::to_string(n));
+    for (int l = 0; l < n; ++l)
+        if (p[l] < -VP3D_X3_PRESCALE_MAX || p[l] > VP3D_X3_PRESCALE_MAX)
+            return fail(VP3D_ERR_ARG, "f16x3 pre-scale: layer " + std::to_string(l) + " has exponent " +
+                                          std::to_string(p[l]) + ", past +-" + std::to_string(VP3D_X3_PRESCALE_MAX));
+    // residual constraint: a block's output is res + relu(bn(z)) with res the block input, so
+    // the expand output (layer 0) and every block's 1x1 output (layers 2, 4, ...) share one exponent
+    for (int l = 2; l < n; l += 2)
+        if (p[l] != p[0])
+            return fail(VP3D_ERR_ARG, "f16x3 pre-scale: layer " + std::to_string(l) + " (a block's 1x1 output) has exponent " +
+                                          std::to_string(p[l]) + " but the residual chain (layer 0, the expand output) has " +
+                                          std::to_string(p[0]) + "; the layers a residual add joins share one exponent");
+    int dev = 0;
+    hipGetDevice(&dev);
+    if (dev != h->device) return fail(VP3D_ERR_STATE, "handle belongs to another device");
+    if (std::equal(p, p + n, h->x3_prescale.begin())) return VP3D_OK;
+    // a forward in flight may still read the vectors about to be rewritten
+    HIP_TRY(hipDeviceSynchronize());
+    const std::vector<int> prev = h->x3_prescale;
+    h->x3_prescale.assign(p, p + n);
+    const int rc = fold_x3(h);
+    if (rc) h->x3_prescale = prev;
+    return rc;
+}
+
+int vp3d_get_x3_prescale(const vp3d_handle* h, int32_t* p, int n) {
+    if (!h) return fail(VP3D_ERR_ARG, "handle is NULL");
+    if (!p) return fail(VP3D_ERR_ARG, "exponents is NULL");
+    if (n != (int)h->x3_prescale.size())
+        return fail(VP3D_ERR_ARG, "f16x3 pre-scale: expected room for " + std::to_string(h->x3_prescale.size()) +
+                                      " exponents, got " + std::to_string(n));
+    std::copy(h->x3_prescale.begin(), h->x3_prescale.end(), p);
+    return VP3D_OK;
+}
+
+// The calibration pass: the fp32 forward with every conv layer's output reduced on the device
+// (act_stats.hip), then the accumulators read back.  Synchronous.
+static int calibrate_impl(vp3d_handle* h, const float* x, int B, int T, vp3d_act_stats* out, void* stream,
+                          const GatherSrc* gs) {
+    if (!out) return fail(VP3D_ERR_ARG, "stats_out is NULL");
+    int dev = 0;
+    hipGetDevice(&dev);
+    if (dev != h->device) return fail(VP3D_ERR_STATE, "handle belongs to another device");
+    std::vector<int> len;
+    if (!layer_lengths(h, T, len))
+        return fail(VP3D_ERR_ARG, "input of " + std::to_string(T) + " frames does not fit the receptive field of " +
+                                      std::to_string(vp3d_receptive_field(h)));
+    const int n = (int)h->layers.size() - 1;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t stat_bytes = (size_t)n * vp3d::kActStatSlots * sizeof(vp3d::ActStats);
+    if (!h->x3_stats) HIP_TRY(hipMalloc((void**)&h->x3_stats, stat_bytes));
+    HIP_TRY(hipMemsetAsync(h->x3_stats, 0, stat_bytes, s));
+    float* y = nullptr;
+    HIP_TRY(hipMalloc((void**)&y, (size_t)B * len.back() * h->layers.back().cout * sizeof(float)));
+    int rc = forward_impl(h, x, B, T, y, VP3D_DTYPE_F32, stream, gs, h->x3_stats);
+    std::vector<vp3d::ActStats> host((size_t)n * vp3d::kActStatSlots);
+    hipError_t e = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = hipMemcpy(host.data(), h->x3_stats, stat_bytes, hipMemcpyDeviceToHost);
+    hipFree(y);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(VP3D_ERR_HIP, std::string("calibration read-back: ") + hipGetErrorString(e));
+    for (int l = 0; l < n; ++l) {
+        const double count = (double)B * len[l] * h->layers[l].cout;
+        unsigned bits = 0;
+        double sumsq = 0.0;
+        unsigned long long small = 0;
+        for (int k = 0; k < vp3d::kActStatSlots; ++k) {
+            const vp3d::ActStats& t = host[(size_t)l * vp3d::kActStatSlots + k];
+            bits = std::max(bits, t.absmax_bits);
+            sumsq += t.sumsq;
+            small += t.small;
+        }
+        float amax;
+        std::memcpy(&amax, &bits, 4);
+        out[l].absmax = (double)amax;
+        out[l].rms = std::sqrt(sumsq / count);
+        out[l].small_share = (double)small / count;
+    }
+    return VP3D_OK;
+}
+
+int vp3d_x3_calibrate(vp3d_handle* h, const float* x, int B, int T, vp3d_act_stats* stats_out, void* stream) {
+    if (!h) return fail(VP3D_ERR_ARG, "handle is NULL");
+    if (!x) return fail(VP3D_ERR_ARG, "x is NULL");
+    if (B <= 0) return fail(VP3D_ERR_ASSERT, "batch must be positive");
+    return calibrate_impl(h, x, B, T, stats_out, stream, nullptr);
+}
+
+int vp3d_x3_calibrate_windows(vp3d_handle* h, const float* kps, int32_t f2, const float* cams, const int64_t* seq_off,
+                              const int32_t* seq_len, const int32_t* pairs, int B, int window, int lead,
+                              vp3d_act_stats* stats_out, void* stream) {
+    if (!h) return fail(VP3D_ERR_ARG, "handle is NULL");
+    if (!kps || !seq_off || !seq_len || !pairs) return fail(VP3D_ERR_ARG, "a device pointer is NULL");
+    if (B <= 0) return fail(VP3D_ERR_ASSERT, "batch must be positive");
+    const int cin = h->cfg.num_joints_in * h->cfg.in_features;
+    if (f2 + (cams ? 12 : 0) != cin)
+        return fail(VP3D_ERR_ASSERT, "frame features (" + std::to_string(f2) + (cams ? " + 12" : "") +
+                                         ") != num_joints_in * in_features (" + std::to_string(cin) + ")");
+    GatherSrc g;
+    g.kps = kps;
+    g.f2 = f2;
+    g.cams = cams;
+    g.seq_off = seq_off;
+    g.seq_len = seq_len;
+    g.pairs = pairs;
+    g.lead = lead;
+    return calibrate_impl(h, nullptr, B, window, stats_out, stream, &g);
 }
 
 int vp3d_profile_enable(vp3d_handle* h, int enable) {

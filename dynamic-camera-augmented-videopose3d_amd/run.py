@@ -432,6 +432,42 @@ def train_main(args, data):
                  0.001, 0.95, save_state=True, resume=resume)
 
 
+def x3_calibrate_refusal(args):
+    """Why --x3-calibrate cannot run with these arguments, or None.  The pre-scale exists on the
+    temporal lifter's f16x3 path only."""
+    if args.x3_calibrate == 0:
+        return None
+    if args.x3_calibrate < 0:
+        return "--x3-calibrate takes a frame count >= 0 (0 = off)"
+    if not args.evaluate:
+        return "--x3-calibrate applies to --evaluate (the eval-mode f16x3 forward)"
+    if args.model_name != "FCN":
+        return (f"--x3-calibrate: --use-model {args.model_name} has no f16x3 pre-scale flag (the temporal "
+                "lifter FCN only; a StackedPoselifter's FCN takes it through calibrate_f16x3)")
+    if args.compute_dtype != "f16x3":
+        return (f"--x3-calibrate chooses the f16x3 activation pre-scale; --compute-dtype {args.compute_dtype} "
+                "has none (use --compute-dtype f16x3)")
+    return None
+
+
+def x3_calibrate(args, model, data, actions, make_generator, action_filter):
+    """--x3-calibrate N: choose the f16x3 pre-scale on the first N output frames of the first
+    evaluated sequence (model.calibrate_f16x3: an fp32 pass with per-layer device statistics)."""
+    for key in actions:
+        if action_filter is not None and not any(key.startswith(a) for a in action_filter):
+            continue
+        gen = make_generator(*_views(data, actions[key]))
+        for _, _, batch_2d, _ in gen.next_epoch():
+            frames = min(int(batch_2d.shape[1]), args.x3_calibrate + model.receptive_field() - 1)
+            with torch.no_grad():
+                p, stats = model.calibrate_f16x3(batch_2d[:, :frames].contiguous())
+            print('INFO: f16x3 pre-scale calibrated on {} frames of {}: chain exponent {}, k-conv exponents {}, '
+                  'largest small_share {:.4f}'.format(frames - model.receptive_field() + 1, key, p[0],
+                                                      p[1::2], max(s["small_share"] for s in stats)))
+            return p
+    raise SystemExit("--x3-calibrate: no sequence to calibrate on")
+
+
 def main(argv=None):
     from common.arguments import parse_args
     from common.generators import UnchunkedGenerator
@@ -444,6 +480,8 @@ def main(argv=None):
         raise KeyError('Invalid model name')  # run.py:392-393
     if stacked and stacked_refusal(args):
         raise SystemExit(stacked_refusal(args))
+    if x3_calibrate_refusal(args):
+        raise SystemExit(x3_calibrate_refusal(args))
     if not torch.cuda.is_available():
         raise SystemExit("run.py evaluates on the MI355X (no CPU fallback)")
     if seq_model and not args.evaluate:
@@ -478,6 +516,8 @@ def main(argv=None):
                                   trajectory=args.trajectory)
 
     action_filter = None if args.actions == "*" else args.actions.split(",")
+    if args.x3_calibrate > 0:
+        x3_calibrate(args, model, data, group_actions(data, subjects), make_generator, action_filter)
     print('Evaluating...')
     if not args.by_subject:
         return run_evaluation(data, group_actions(data, subjects), make_generator, model,

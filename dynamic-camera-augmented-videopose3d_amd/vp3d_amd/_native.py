@@ -45,6 +45,7 @@ EXPORTS = [
     "vp3d_receptive_field", "vp3d_total_causal_shift", "vp3d_out_frames",
     "vp3d_reserve", "vp3d_forward", "vp3d_forward_windows", "vp3d_sync_status", "vp3d_profile_enable",
     "vp3d_layer_count",
+    "vp3d_set_x3_prescale", "vp3d_get_x3_prescale", "vp3d_x3_calibrate", "vp3d_x3_calibrate_windows",
     "vp3d_profile_read", "vp3d_profile_reset", "vp3d_profile_layers", "vp3d_normalize_screen",
     "vp3d_normalize_screen_f64", "vp3d_image_coordinates", "vp3d_camera_matrices", "vp3d_world_to_camera",
     "vp3d_gather_windows", "vp3d_mpjpe_accumulate", "vp3d_pose_metrics", "vp3d_project_to_2d", "vp3d_last_error", "vp3d_abi_version",
@@ -74,6 +75,17 @@ class vp3d_cfg(ctypes.Structure):
         ("dense", ctypes.c_int32),
         ("variant", ctypes.c_int32),
         ("bn_eps", ctypes.c_float),
+    ]
+
+
+X3_PRESCALE_MAX = 24
+
+
+class vp3d_act_stats(ctypes.Structure):
+    _fields_ = [
+        ("absmax", ctypes.c_double),
+        ("rms", ctypes.c_double),
+        ("small_share", ctypes.c_double),
     ]
 
 
@@ -135,6 +147,11 @@ _SIGNATURES = {
     "vp3d_profile_enable": (_int, [_vp, _int]),
     "vp3d_sync_status": (_int, [_vp, _vp]),
     "vp3d_layer_count": (_int, [_vp]),
+    "vp3d_set_x3_prescale": (_int, [_vp, ctypes.POINTER(_i32), _int]),
+    "vp3d_get_x3_prescale": (_int, [_vp, ctypes.POINTER(_i32), _int]),
+    "vp3d_x3_calibrate": (_int, [_vp, _vp, _int, _int, ctypes.POINTER(vp3d_act_stats), _vp]),
+    "vp3d_x3_calibrate_windows": (_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _int, _int, _int,
+                                         ctypes.POINTER(vp3d_act_stats), _vp]),
     "vp3d_profile_read": (_int, [_vp, _vp, _vp, _vp]),
     "vp3d_profile_reset": (_int, [_vp]),
     "vp3d_profile_layers": (_int, [_vp, ctypes.c_uint64]),

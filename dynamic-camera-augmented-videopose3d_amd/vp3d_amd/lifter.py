@@ -138,6 +138,55 @@ class NativeLifter:
                 N.DTYPES[dtype], N.stream_ptr(self.device)), "vp3d_forward_windows")
         return out
 
+    # ---- f16x3 activation pre-scale ----
+    def set_x3_prescale(self, p) -> None:
+        """One power-of-two exponent per conv layer output (n_layers - 1: the shrink has none):
+        layer l's f16x3 stored rows hold a * 2^p[l] (vp3d_set_x3_prescale).  None or all zeros
+        clears it.  Raises on a wrong length, |p| > 24 or a vector breaking the residual chain."""
+        n = self.n_layers - 1
+        vals = [0] * n if p is None else [int(v) for v in p]
+        arr = (ctypes.c_int32 * len(vals))(*vals)
+        with torch.cuda.device(self.device):
+            N.check(self._lib.vp3d_set_x3_prescale(self._h, arr, len(vals)), "vp3d_set_x3_prescale")
+
+    def x3_prescale(self) -> List[int]:
+        n = self.n_layers - 1
+        arr = (ctypes.c_int32 * n)()
+        N.check(self._lib.vp3d_get_x3_prescale(self._h, arr, n), "vp3d_get_x3_prescale")
+        return list(arr)
+
+    def calibrate_x3(self, x: torch.Tensor | None = None, *, seqs=None, pairs: torch.Tensor | None = None,
+                     window: int | None = None, lead: int = 0, concat_cams: bool = False) -> List[dict]:
+        """Per-layer statistics of the fp32 forward (vp3d_x3_calibrate) on x: (B, T, J_in, F), or
+        on the windows `pairs` gathers from `seqs` (as forward_windows).  One dict per conv
+        layer output: absmax, rms, small_share (the share of non-zero values under 2^-3)."""
+        n = self.n_layers - 1
+        stats = (N.vp3d_act_stats * n)()
+        if x is not None:
+            if x.device != self.device:
+                raise RuntimeError(f"input on {x.device}, model on {self.device}")
+            x = x.float().contiguous()
+            with torch.cuda.device(self.device):
+                N.check(self._lib.vp3d_x3_calibrate(self._h, x.data_ptr(), int(x.shape[0]), int(x.shape[1]),
+                                                    stats, N.stream_ptr(self.device)), "vp3d_x3_calibrate")
+        else:
+            if seqs is None or pairs is None or window is None:
+                raise ValueError("calibrate_x3 takes x, or seqs + pairs + window")
+            if pairs.device != self.device or seqs.kps.device != self.device:
+                raise RuntimeError("pairs / sequences must live on the model's device")
+            pairs = pairs.contiguous().to(torch.int32)
+            cams = None
+            if concat_cams:
+                if seqs.cam is None:
+                    raise ValueError("no cameras loaded")
+                cams = seqs.cam.data_ptr()
+            with torch.cuda.device(self.device):
+                N.check(self._lib.vp3d_x3_calibrate_windows(
+                    self._h, seqs.kps.data_ptr(), seqs.f2, cams, seqs.seq_off.data_ptr(),
+                    seqs.seq_len.data_ptr(), pairs.data_ptr(), int(pairs.shape[0]), int(window), int(lead),
+                    stats, N.stream_ptr(self.device)), "vp3d_x3_calibrate_windows")
+        return [dict(layer=i, absmax=s.absmax, rms=s.rms, small_share=s.small_share) for i, s in enumerate(stats)]
+
     def sync_status(self) -> None:
         """Synchronise the current stream; raise RuntimeError once if a launch of this lifter
         reported a device-side fault, and clear it (vp3d_sync_status).  The fault kinds:

@@ -147,6 +147,49 @@ int vp3d_forward_windows(vp3d_handle* h, const float* kps, int32_t f2, const flo
                          const int64_t* seq_off, const int32_t* seq_len, const int32_t* pairs, int B,
                          int window, int lead, float* y, int dtype, void* stream);
 
+/* ---- f16x3 activation pre-scale (opt-in; no reference counterpart) ----
+ * The split-fp16 path stores every activation as hi = f16(a), lo = f16(a - hi); lo is an f16
+ * subnormal for |a| < 2^-3, an absolute floor of 2^-25 per stored value, so a checkpoint whose
+ * hidden activations are small loses accuracy silently.  An exact power-of-two pre-scale per
+ * conv layer output moves the stored rows back into range: layer l's stored rows hold
+ * a * 2^p[l], folded into the f16x3 epilogue's scale and shift when the weights are packed
+ * (the eval BatchNorm + ReLU of TemporalModel.py:102-119 commute with a positive scale), the
+ * next layer absorbing the inverse and the shrink (TemporalModel.py:75) the last one.  Nothing
+ * changes per forward; the fp32 / bf16 / fp16 paths never see it. */
+#define VP3D_X3_PRESCALE_MAX 24
+
+/* Set one exponent per conv layer output: n = vp3d_layer_count(h) - 1 (the shrink has none),
+ * in layer order (expand, then k-conv and 1x1 of each block, TemporalModel.py:102-119).  The
+ * residual add (TemporalModel.py:132 / :192) joins the expand output and every block's 1x1
+ * output, so layers 0, 2, 4, ... must share one exponent ("the chain"); each k-conv output
+ * (layers 1, 3, ...) has its own.  VP3D_ERR_ARG (vp3d_last_error names the layer) for a vector
+ * that breaks this, for |p| > VP3D_X3_PRESCALE_MAX, or for a wrong n.  All zeros restores the
+ * unscaled state bit for bit.  Kept across vp3d_load_weights.  Synchronises the device when
+ * the exponents change.  A pre-scale that pushes a stored value past 65,504 is caught by the
+ * f16x3 range guard (vp3d_sync_status). */
+int vp3d_set_x3_prescale(vp3d_handle* h, const int32_t* p, int n);
+int vp3d_get_x3_prescale(const vp3d_handle* h, int32_t* p, int n);
+
+/* Per-layer statistics of the calibration pass. */
+typedef struct vp3d_act_stats {
+    double absmax;      /* max |a| over the layer's output; inf / NaN if one occurred        */
+    double rms;         /* sqrt(mean a^2), summed in f64                                      */
+    double small_share; /* share of the values with a != 0 and |a| < 2^-3 (subnormal lo half) */
+} vp3d_act_stats;
+
+/* Calibration: run the fp32 forward (TemporalModel.py:62-76) on x (device f32, (B, T, J_in, F))
+ * and reduce every conv layer's output on the device (after BN, ReLU and the residual add of
+ * TemporalModel.py:102-119,126-138 -- the values the f16x3 path stores) into
+ * stats_out[0 .. vp3d_layer_count(h) - 2], a HOST array.  The fp32 path measures, never the
+ * f16x3 one (it is the degraded thing being measured); the handle's pre-scale is neither
+ * read nor changed.  Synchronous. */
+int vp3d_x3_calibrate(vp3d_handle* h, const float* x, int B, int T, vp3d_act_stats* stats_out, void* stream);
+/* The same on windows gathered from device-resident sequences (arguments as
+ * vp3d_forward_windows; generators.py:102-137, CamTransformer.py:187-190). */
+int vp3d_x3_calibrate_windows(vp3d_handle* h, const float* kps, int32_t f2, const float* cams,
+                              const int64_t* seq_off, const int32_t* seq_len, const int32_t* pairs, int B,
+                              int window, int lead, vp3d_act_stats* stats_out, void* stream);
+
 /* ---- per-layer timing (HIP events recorded on the launch stream) ---- */
 int vp3d_profile_enable(vp3d_handle* h, int enable);
 /* Restrict the timing to the layers in `mask` (bit i = layer i; all by default), e.g.
