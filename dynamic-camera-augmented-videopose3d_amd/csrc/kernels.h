@@ -176,6 +176,34 @@ struct StreamLayerParams {
 };
 hipError_t launch_stream_gemv(const StreamLayerParams& q, Act wtype, hipStream_t s);
 
+// Batched causal streaming step (stream_batch.hip): one skinny-GEMM layer per launch for S
+// stream slots, each at its own position t[s].  Slot s reads its own rings / vectors at
+// `*_stride` floats per slot; a slot with active[s] == 0 stores nothing.
+constexpr int kStreamBatchMax = 64;  // slots per launch (four 16-row MFMA tiles)
+struct StreamBatchParams {
+    const void* W;            // packed weights [Np][Kp] of the step dtype (shared with the single stream)
+    const float* scale;       // [N]
+    const float* shift;       // [N]
+    int N, K, Kp, cin, taps, dil, relu;
+    int S;                    // slots, 1..kStreamBatchMax
+    const float* in;          // per slot: input ring (in_R slots of cin floats) or plain vector (in_R == 0)
+    int in_R;
+    int64_t in_stride;
+    const float* in_frame;    // expand layer: the new frames (S, cin), read for tap time t[s]
+    float* in_ring_w;         // expand layer: the slots' frame rings the new frames are appended to
+    const float* res;         // per slot: residual ring (block input) or nullptr
+    int res_R;
+    int64_t res_stride;
+    float* out;               // per slot: output ring (out_R slots of N floats) or plain vector
+    int out_R;
+    int64_t out_stride;
+    const int* t;             // [S] stream positions (read only: advanced by the trailing launch)
+    const int* active;        // [S] nonzero = the slot takes part in this step
+};
+hipError_t launch_stream_batch(const StreamBatchParams& q, Act wtype, hipStream_t s);
+// the step's last launch: t[s] += 1 for every active slot
+hipError_t launch_stream_batch_advance(int* t, const int* active, int S, hipStream_t s);
+
 // Causal streaming, persistent form (stream_persist.hip): one launch runs `steps` frames;
 // workgroup g owns channels [g*CPW, (g+1)*CPW) of every layer with their 16-bit weights
 // resident in LDS, the layer outputs handed to every workgroup through {tag, value}

@@ -1834,6 +1834,249 @@ int vp3d_stream_destroy(vp3d_stream* st) {
     return VP3D_OK;
 }
 
+// ---- batched causal streaming (stream_batch.hip) ----
+
+}  // extern "C"
+
+struct vp3d_mstream {
+    vp3d_handle* h = nullptr;
+    int dtype = VP3D_DTYPE_F16;
+    int S = 0;
+    int* pos = nullptr;        // device: [S] stream positions, then [S] the step's active words
+    float* frames = nullptr;   // device io: (S, J_in*F)
+    float* poses = nullptr;    // device io: (S, J_out*3)
+    float* rings = nullptr;    // S x (every ring of one stream)
+    float* scratch = nullptr;  // S x C k-conv outputs, then S x C last-block outputs
+    std::vector<StreamBatchParams> steps;
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+};
+
+namespace {
+
+int32_t* mstream_active(vp3d_mstream* m) { return (int32_t*)(m->pos + m->S); }
+
+// one step on the io buffers: a launch per layer, then the positions
+int mstream_launch(vp3d_mstream* m, hipStream_t s) {
+    const Act wt = m->dtype == VP3D_DTYPE_F32 ? Act::F32 : (m->dtype == VP3D_DTYPE_BF16 ? Act::BF16 : Act::F16);
+    for (const StreamBatchParams& q : m->steps) HIP_TRY(launch_stream_batch(q, wt, s));
+    HIP_TRY(launch_stream_batch_advance(m->pos, mstream_active(m), m->S, s));
+    return VP3D_OK;
+}
+
+void mstream_free(vp3d_mstream* m) {
+    if (m->exec) hipGraphExecDestroy(m->exec);
+    if (m->graph) hipGraphDestroy(m->graph);
+    hipFree(m->pos);
+    hipFree(m->frames);
+    hipFree(m->poses);
+    hipFree(m->rings);
+    hipFree(m->scratch);
+    delete m;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vp3d_mstream_create(vp3d_handle* h, int dtype, int n_streams, vp3d_mstream** out) {
+    if (!h || !out) return fail(VP3D_ERR_ARG, "NULL argument");
+    *out = nullptr;
+    if (dtype < 0 || dtype > 2) return fail(VP3D_ERR_ARG, "unknown dtype");
+    if (n_streams < 1 || n_streams > VP3D_MSTREAM_MAX)
+        return fail(VP3D_ERR_ARG, "n_streams must be 1.." + std::to_string(VP3D_MSTREAM_MAX));
+    static_assert(VP3D_MSTREAM_MAX == kStreamBatchMax, "the kernel's slot limit is the ABI's");
+    if (h->cfg.variant != VP3D_VARIANT_DILATED || !h->cfg.causal)
+        return fail(VP3D_ERR_ARG, "streaming needs a causal dilated TemporalModel");
+    for (const Layer& L : h->layers)
+        if (L.Kp > 4096) return fail(VP3D_ERR_ARG, "streaming supports K <= 4096 per layer");
+    int dev = 0;
+    hipGetDevice(&dev);
+    if (dev != h->device) return fail(VP3D_ERR_STATE, "handle belongs to another device");
+
+    vp3d_mstream* m = new vp3d_mstream();
+    m->h = h;
+    m->dtype = dtype;
+    m->S = n_streams;
+    const int S = n_streams;
+    const int C = h->cfg.channels;
+    const int nl = (int)h->layers.size();
+    const int nb = h->cfg.n_widths - 1;
+    const int cin0 = h->layers[0].cin, nout = h->layers.back().cout;
+    // ring i of a slot holds the input of layer (expand: raw frames) / block i, the single
+    // stream's sizes; offsets rounded to 16 bytes so that rows of 4 | cin floats stay aligned
+    std::vector<int> ring_len;
+    std::vector<size_t> ring_off;
+    size_t ring_floats = 0;
+    auto add_ring = [&](const Layer& L, int width) {
+        ring_len.push_back(pow2_at_least((L.taps - 1) * L.dil + 1));
+        ring_off.push_back(ring_floats);
+        ring_floats += ((size_t)ring_len.back() * width + 3) / 4 * 4;
+    };
+    add_ring(h->layers[0], cin0);
+    for (int b = 1; b <= nb; ++b) add_ring(h->layers[2 * b - 1], C);
+    if (hipMalloc(&m->pos, 8 * (size_t)S) != hipSuccess || hipMalloc(&m->frames, 4 * (size_t)S * cin0) != hipSuccess ||
+        hipMalloc(&m->poses, 4 * (size_t)S * nout) != hipSuccess ||
+        hipMalloc(&m->rings, 4 * (size_t)S * ring_floats) != hipSuccess ||
+        hipMalloc(&m->scratch, 8 * (size_t)S * C) != hipSuccess) {
+        mstream_free(m);
+        return fail(VP3D_ERR_OOM, "batched stream buffers");
+    }
+    hipMemset(m->pos, 0, 8 * (size_t)S);
+    hipMemset(m->frames, 0, 4 * (size_t)S * cin0);
+    hipMemset(m->poses, 0, 4 * (size_t)S * nout);
+    hipMemset(m->rings, 0, 4 * (size_t)S * ring_floats);
+    float* hbuf = m->scratch;                  // (S, C) k-conv output of the current block
+    float* xlast = m->scratch + (size_t)S * C;  // (S, C) output of the last block (or of expand if nb == 0)
+
+    auto base = [&](const Layer& L) {
+        StreamBatchParams q{};
+        q.W = dtype == VP3D_DTYPE_F32 ? (const void*)L.w32 : (dtype == VP3D_DTYPE_BF16 ? (const void*)L.wbf : (const void*)L.wh);
+        q.scale = L.scale;
+        q.shift = L.shift;
+        q.N = L.cout;
+        q.K = L.K;
+        q.Kp = L.Kp;
+        q.cin = L.cin;
+        q.taps = L.taps;
+        q.dil = L.dil;
+        q.relu = L.relu ? 1 : 0;
+        q.S = S;
+        q.t = m->pos;
+        q.active = mstream_active(m);
+        return q;
+    };
+    auto ring_in = [&](StreamBatchParams& q, int i) {
+        q.in = m->rings + ring_off[i];
+        q.in_R = ring_len[i];
+        q.in_stride = (int64_t)ring_floats;
+    };
+    auto plain_in = [&](StreamBatchParams& q, const float* v) {
+        q.in = v;
+        q.in_stride = C;
+    };
+    // the output of the layer that feeds block b (ring b), or the last block's plain rows
+    auto out_to = [&](StreamBatchParams& q, int b) {
+        if (b <= nb) {
+            q.out = m->rings + ring_off[b];
+            q.out_R = ring_len[b];
+            q.out_stride = (int64_t)ring_floats;
+        } else {
+            q.out = xlast;
+            q.out_stride = C;
+        }
+    };
+    {
+        StreamBatchParams q = base(h->layers[0]);
+        ring_in(q, 0);
+        q.in_frame = m->frames;
+        q.in_ring_w = m->rings + ring_off[0];
+        out_to(q, 1);
+        m->steps.push_back(q);
+    }
+    for (int b = 1; b <= nb; ++b) {
+        StreamBatchParams k = base(h->layers[2 * b - 1]);
+        ring_in(k, b);
+        k.out = hbuf;
+        k.out_stride = C;
+        m->steps.push_back(k);
+        StreamBatchParams pw = base(h->layers[2 * b]);
+        plain_in(pw, hbuf);
+        pw.res = m->rings + ring_off[b];
+        pw.res_R = ring_len[b];
+        pw.res_stride = (int64_t)ring_floats;
+        out_to(pw, b + 1);
+        m->steps.push_back(pw);
+    }
+    {
+        StreamBatchParams q = base(h->layers[nl - 1]);
+        plain_in(q, xlast);
+        q.out = m->poses;
+        q.out_stride = nout;
+        m->steps.push_back(q);
+    }
+    hipDeviceSynchronize();  // setup memsets (legacy stream) before any launch on another stream
+    *out = m;
+    return VP3D_OK;
+}
+
+int vp3d_mstream_io(vp3d_mstream* m, float** frames, int32_t** active, float** poses) {
+    if (!m) return fail(VP3D_ERR_ARG, "mstream is NULL");
+    if (frames) *frames = m->frames;
+    if (active) *active = mstream_active(m);
+    if (poses) *poses = m->poses;
+    return VP3D_OK;
+}
+
+int vp3d_mstream_step(vp3d_mstream* m, const float* frames, const int32_t* active, float* poses, void* stream) {
+    if (!m) return fail(VP3D_ERR_ARG, "mstream is NULL");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t cin0 = m->h->layers[0].cin, nout = m->h->layers.back().cout;
+    if (frames) HIP_TRY(hipMemcpyAsync(m->frames, frames, 4 * m->S * cin0, hipMemcpyDeviceToDevice, s));
+    if (active)
+        HIP_TRY(hipMemcpyAsync(mstream_active(m), active, 4 * (size_t)m->S, hipMemcpyDeviceToDevice, s));
+    else if (frames)
+        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)mstream_active(m), 1, (size_t)m->S, s));
+    int rc = mstream_launch(m, s);
+    if (rc) return rc;
+    if (poses) HIP_TRY(hipMemcpyAsync(poses, m->poses, 4 * m->S * nout, hipMemcpyDeviceToDevice, s));
+    return VP3D_OK;
+}
+
+int vp3d_mstream_reset(vp3d_mstream* m, int slot, void* stream) {
+    if (!m) return fail(VP3D_ERR_ARG, "mstream is NULL");
+    if (slot < -1 || slot >= m->S) return fail(VP3D_ERR_ARG, "slot must be -1 or 0..n_streams-1");
+    if (slot < 0)
+        HIP_TRY(hipMemsetAsync(m->pos, 0, 4 * (size_t)m->S, (hipStream_t)stream));
+    else
+        HIP_TRY(hipMemsetAsync(m->pos + slot, 0, 4, (hipStream_t)stream));
+    return VP3D_OK;
+}
+
+int vp3d_mstream_frames_seen(vp3d_mstream* m, int64_t* out) {
+    if (!m || !out) return fail(VP3D_ERR_ARG, "NULL argument");
+    std::vector<int> t((size_t)m->S);
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(t.data(), m->pos, 4 * (size_t)m->S, hipMemcpyDeviceToHost));
+    for (int s = 0; s < m->S; ++s) out[s] = t[s];
+    return VP3D_OK;
+}
+
+int vp3d_mstream_graph_capture(vp3d_mstream* m, void* stream) {
+    if (!m) return fail(VP3D_ERR_ARG, "mstream is NULL");
+    if (!stream) return fail(VP3D_ERR_ARG, "graph capture needs a non-default stream");
+    hipStream_t s = (hipStream_t)stream;
+    if (m->exec) {
+        hipGraphExecDestroy(m->exec);
+        m->exec = nullptr;
+    }
+    if (m->graph) {
+        hipGraphDestroy(m->graph);
+        m->graph = nullptr;
+    }
+    HIP_TRY(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+    int rc = mstream_launch(m, s);
+    hipGraph_t g = nullptr;
+    hipError_t e = hipStreamEndCapture(s, &g);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(VP3D_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
+    m->graph = g;
+    HIP_TRY(hipGraphInstantiate(&m->exec, g, nullptr, nullptr, 0));
+    return VP3D_OK;
+}
+
+int vp3d_mstream_graph_launch(vp3d_mstream* m, void* stream) {
+    if (!m || !m->exec) return fail(VP3D_ERR_STATE, "no captured graph");
+    HIP_TRY(hipGraphLaunch(m->exec, (hipStream_t)stream));
+    return VP3D_OK;
+}
+
+int vp3d_mstream_destroy(vp3d_mstream* m) {
+    if (!m) return VP3D_OK;
+    mstream_free(m);
+    return VP3D_OK;
+}
+
 // ---- on-device input path ----
 
 int vp3d_normalize_screen(const float* x, int64_t n_points, int32_t w, int32_t h, float* out,

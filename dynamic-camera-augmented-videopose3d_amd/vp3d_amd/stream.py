@@ -9,6 +9,9 @@ GEMV launch per layer (csrc/stream_step.hip).  For a causal dilated TemporalMode
 (reference TemporalModel.py:79-138 with causal=True), pose k of the stream equals
 frame k of the reference's whole-sequence evaluation of the edge-padded
 sequence (UnchunkedGenerator, generators.py:193-198, causal_shift = pad).
+
+CausalStreamBatch advances many such streams in one step (vp3d_mstream,
+csrc/stream_batch.hip): one skinny-GEMM launch per layer over all of them.
 """
 from __future__ import annotations
 
@@ -183,14 +186,115 @@ class Serving:
         return False
 
 
+class CausalStreamBatch:
+    """`n_streams` independent causal streams ("slots") of one lifter advanced together.
+
+    Wraps vp3d_mstream (include/vp3d.h): every layer of a step is one skinny GEMM over the
+    slots (csrc/stream_batch.hip: exact f32 MFMA, f32 activations, 16-bit weights widened in
+    registers), so a step reads the weights once however many slots take part.  Each slot has
+    its own position and rings; a slot that is inactive in a step consumes no frame and keeps
+    its pose row.  Slot s's k-th active step equals frame k of the reference's whole-sequence
+    causal evaluation of the frames that slot consumed, as for a CausalStream -- which stays
+    the path for one stream.
+    """
+
+    def __init__(self, lifter, n_streams: int, dtype: str = "fp16"):
+        """lifter: a NativeLifter (``model.native_lifter()``) of a causal TemporalModel."""
+        self._lib = N.load()
+        self.lifter = lifter
+        self.device = lifter.device
+        self.dtype = dtype
+        self.n_streams = int(n_streams)
+        self._m = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            N.check(self._lib.vp3d_mstream_create(lifter._h, N.DTYPES[dtype], self.n_streams,
+                                                  ctypes.byref(self._m)), "vp3d_mstream_create")
+        f, a, p = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+        N.check(self._lib.vp3d_mstream_io(self._m, ctypes.byref(f), ctypes.byref(a), ctypes.byref(p)))
+        self._io_ptrs = (f.value, a.value, p.value)
+        self.j_in, self.in_features = lifter.cfg.num_joints_in, lifter.cfg.in_features
+        self.n_in = self.j_in * self.in_features
+        self.n_out = lifter.cfg.num_joints_out * 3
+        self._graph_stream = None
+
+    def step(self, frames: torch.Tensor, active: torch.Tensor | None = None,
+             out: torch.Tensor | None = None) -> torch.Tensor:
+        """frames: (S, J_in, F) float32 on the device; active: (S,) device tensor of an integer
+        or bool dtype (nonzero = the slot consumes its frame), None = every slot
+        -> (S, J_out, 3) float32; the row of an inactive slot is that of its last active step."""
+        S = self.n_streams
+        if not frames.is_cuda or (active is not None and not active.is_cuda):
+            raise RuntimeError("vp3d: stream frames must be HIP device tensors (no CPU fallback)")
+        if tuple(frames.shape) != (S, self.j_in, self.in_features):
+            raise RuntimeError(f"vp3d: frames must be ({S}, {self.j_in}, {self.in_features}), got {tuple(frames.shape)}")
+        frames = frames.contiguous().float()
+        a_ptr = None
+        if active is not None:
+            if tuple(active.shape) != (S,) or active.dtype.is_floating_point or active.dtype.is_complex:
+                raise RuntimeError(f"vp3d: active must be an integer or bool tensor of shape ({S},)")
+            active = (active != 0).to(torch.int32).contiguous()
+            a_ptr = active.data_ptr()
+        if out is None:
+            out = torch.empty((S, self.n_out // 3, 3), dtype=torch.float32, device=self.device)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.numel() == S * self.n_out
+        with torch.cuda.device(self.device):
+            N.check(self._lib.vp3d_mstream_step(self._m, frames.data_ptr(), a_ptr, out.data_ptr(),
+                                                N.stream_ptr(self.device)), "vp3d_mstream_step")
+        return out
+
+    def reset(self, slot: int | None = None) -> None:
+        """Restart one slot (None: every slot): its next frame is frame 0 of a new sequence."""
+        with torch.cuda.device(self.device):
+            N.check(self._lib.vp3d_mstream_reset(self._m, -1 if slot is None else int(slot),
+                                                 N.stream_ptr(self.device)), "vp3d_mstream_reset")
+
+    def frames_seen(self) -> np.ndarray:
+        """Frames consumed so far by each slot: (S,) int64 (synchronises)."""
+        out = np.zeros(self.n_streams, dtype=np.int64)
+        with torch.cuda.device(self.device):
+            N.check(self._lib.vp3d_mstream_frames_seen(self._m, out.ctypes.data), "vp3d_mstream_frames_seen")
+        return out
+
+    # ---- hipGraph replay: one step reading / writing the io buffers ----
+    def io_tensors(self):
+        """(frames (S, J_in*F) float32, active (S,) int32, poses (S, J_out*3) float32) views of
+        the device buffers a replayed step reads and writes."""
+        S = self.n_streams
+        f, a, p = self._io_ptrs
+        return (_wrap(f, S * self.n_in, self.device).view(S, self.n_in),
+                _wrap(a, S, self.device, "<i4"),
+                _wrap(p, S * self.n_out, self.device).view(S, self.n_out))
+
+    def capture(self, stream: torch.cuda.Stream) -> None:
+        """Capture one step into a hipGraph on `stream` (not the default stream)."""
+        self._graph_stream = stream
+        with torch.cuda.device(self.device):
+            N.check(self._lib.vp3d_mstream_graph_capture(self._m, stream.cuda_stream), "vp3d_mstream_graph_capture")
+
+    def replay(self, stream: torch.cuda.Stream | None = None) -> None:
+        s = stream if stream is not None else self._graph_stream
+        N.check(self._lib.vp3d_mstream_graph_launch(self._m, s.cuda_stream), "vp3d_mstream_graph_launch")
+
+    def close(self) -> None:
+        if self._m:
+            self._lib.vp3d_mstream_destroy(self._m)
+            self._m = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class _DevBuf:
     """Minimal __cuda_array_interface__ exporter for a raw device pointer."""
 
-    def __init__(self, ptr: int, n: int):
-        self.__cuda_array_interface__ = {"shape": (n,), "typestr": "<f4", "data": (ptr, False),
+    def __init__(self, ptr: int, n: int, typestr: str = "<f4"):
+        self.__cuda_array_interface__ = {"shape": (n,), "typestr": typestr, "data": (ptr, False),
                                          "version": 2, "strides": None}
 
 
-def _wrap(ptr: int, n: int, device) -> torch.Tensor:
+def _wrap(ptr: int, n: int, device, typestr: str = "<f4") -> torch.Tensor:
     with torch.cuda.device(device):
-        return torch.as_tensor(_DevBuf(ptr, n), device=device)
+        return torch.as_tensor(_DevBuf(ptr, n, typestr), device=device)

@@ -283,6 +283,46 @@ int vp3d_stream_serve_end(vp3d_stream* s, void* stream);
 int vp3d_stream_trace(vp3d_stream* s, uint64_t* out, int64_t capacity, int32_t* role_first_wg, int32_t* n_roles,
                       int32_t* frames);
 
+/* ---- batched causal streaming: many streams advance in one step ----
+ * n_streams independent causal streams ("slots") of one model, each with its own position
+ * and its own rings, advanced together: every layer of a step is one skinny GEMM (slots x K
+ * by K x channels, exact f32 MFMA, f32 activations; 16-bit weights widened in registers), so
+ * the weights are read once per step however many slots take part (stream_batch.hip).  Slot
+ * s's k-th active step equals frame k of the reference's whole-sequence causal evaluation of
+ * the frames that slot consumed (TemporalModel.py:79-138 with causal=True, UnchunkedGenerator
+ * edge padding, generators.py:193-198), as for a vp3d_stream.  The single stream above
+ * remains the one-stream path. */
+#define VP3D_MSTREAM_MAX 64
+typedef struct vp3d_mstream vp3d_mstream;
+
+/* Accepts what the per-layer-launch form of vp3d_stream_create accepts (a causal dilated or
+ * dense TemporalModel, K <= 4096 per layer, dtype F32 / F16 / BF16) with the same status
+ * codes, and 1 <= n_streams <= VP3D_MSTREAM_MAX (else VP3D_ERR_ARG).  Shares the handle's
+ * device weights: a vp3d_load_weights is seen by the next step. */
+int vp3d_mstream_create(vp3d_handle* h, int dtype, int n_streams, vp3d_mstream** out);
+/* The device io buffers a step reads / writes: frames (S, J_in * F) f32, active (S) int32
+ * (nonzero = the slot consumes its frame in this step), poses (S, J_out * 3) f32. */
+int vp3d_mstream_io(vp3d_mstream* m, float** frames, int32_t** active, float** poses);
+/* One step of every active slot (the reference's model(inputs_2d) on each slot's next frame,
+ * run.py:689-724, one frame at a time).  frames / active / poses: device pointers copied into
+ * / out of the io buffers asynchronously, or NULL to use the io buffers as they are; active
+ * == NULL with frames != NULL means every slot is active.  An inactive slot stores nothing:
+ * no ring slot, no position change, and its pose row keeps the value of its last active step. */
+int vp3d_mstream_step(vp3d_mstream* m, const float* frames, const int32_t* active, float* poses, void* stream);
+/* Restart slot `slot` (-1 = every slot): its next frame is frame 0 (a new sequence through
+ * the reference's generator).  Async on `stream`; rings are not cleared (step 0 rewrites
+ * time 0 before any tap reads it). */
+int vp3d_mstream_reset(vp3d_mstream* m, int slot, void* stream);
+/* Frames consumed so far by each slot (host array of n_streams entries; synchronises with
+ * the device). */
+int vp3d_mstream_frames_seen(vp3d_mstream* m, int64_t* out);
+/* Capture one step (reading / writing the io buffers) into a hipGraph on `stream` (not the
+ * legacy default stream): a linear chain of kernel nodes.  Replay with
+ * vp3d_mstream_graph_launch. */
+int vp3d_mstream_graph_capture(vp3d_mstream* m, void* stream);
+int vp3d_mstream_graph_launch(vp3d_mstream* m, void* stream);
+int vp3d_mstream_destroy(vp3d_mstream* m);
+
 /* ---- training step (run.py:451-487, :662) ----
  * The reference trains TemporalModel in train mode: BatchNorm1d on batch
  * statistics with a running-stat update (TemporalModel.py:117,119; momentum
