@@ -258,6 +258,13 @@ class TemporalModelBase(nn.Module):
             raise NotImplementedError("vp3d: per-layer BatchNorm momenta differ (set_bn_momentum sets one)")
         if any(not bn.track_running_stats or not bn.training for bn in bns):
             raise NotImplementedError("vp3d: train mode needs every BatchNorm training with running stats")
+        # the frame count shrinks from layer to layer, so the last block's BatchNorm sees the
+        # fewest values per channel, batch x output frames.  With one, F.batch_norm refuses to
+        # train (a variance of one value); raise as it does, before any buffer is touched
+        T_out = self._out_frames(int(x.shape[1]))
+        if int(x.shape[0]) * T_out == 1:
+            raise ValueError("Expected more than 1 value per channel when training, got input size "
+                             f"{torch.Size([1, self.channels, 1])}")
         # BatchNorm1d.forward: count the batch; cumulative average when momentum is None
         for bn in bns:
             bn.num_batches_tracked.add_(1)
@@ -269,7 +276,6 @@ class TemporalModelBase(nn.Module):
                 raise RuntimeError("vp3d: parameters must be contiguous float32 tensors on the input's device")
         trainable = tuple(isinstance(t, nn.Parameter) and t.requires_grad for t in tensors)
         trainer = self.native_trainer(x.device)
-        T_out = self._out_frames(int(x.shape[1]))
         seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if self.drop.p > 0 else 0
         x = x.contiguous().float()
         return TrainStep.apply(trainer, float(self.drop.p), float(factor), seed, T_out, trainable, x, *tensors)

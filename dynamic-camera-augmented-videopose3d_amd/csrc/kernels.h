@@ -400,6 +400,7 @@ struct AdamHyper {
     int amsgrad;
 };
 int64_t train_reduce_part_doubles(int64_t M, int C);
+int64_t train_reduce_chunks(int64_t M, int C);  // row chunks a reduction over exactly M rows launches
 // mode 0: forward [cout][k*cin+c]; 1: flipped-tap dgrad [cin][(taps-1-k)*cout+o]; 2: [k*cin+c][cout]
 hipError_t launch_pack_weights(const float* w, int cout, int cin, int taps, int mode, int Kp, float* out,
                                hipStream_t s);

@@ -256,6 +256,11 @@ int64_t vp3d_train_layer_rows(const vp3d_trainer* t, int layer) {
     return (int64_t)t->B * t->len[layer];
 }
 
+int64_t vp3d_train_reduce_doubles(int64_t rows, int channels, int reserved) {
+    if (rows < 0 || channels <= 0) return -1;
+    return reserved ? train_reduce_part_doubles(rows, channels) : train_reduce_chunks(rows, channels) * 2 * channels;
+}
+
 int vp3d_train_forward(vp3d_trainer* t, float* const* params, int n_params, const float* x, int B, int T,
                        float dropout_p, double momentum, uint64_t seed, float* y, void* stream) {
     if (!t) return fail(VP3D_ERR_ARG, "trainer is NULL");

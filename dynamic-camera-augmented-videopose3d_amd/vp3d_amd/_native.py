@@ -59,7 +59,7 @@ EXPORTS = [
     "vp3d_mstream_frames_seen", "vp3d_mstream_graph_capture", "vp3d_mstream_graph_launch",
     "vp3d_mstream_destroy",
     "vp3d_trainer_create", "vp3d_trainer_destroy", "vp3d_train_forward", "vp3d_train_backward",
-    "vp3d_train_dropout_mask", "vp3d_train_relu_mask", "vp3d_train_layer_rows", "vp3d_adam_step", "vp3d_mpjpe_backward",
+    "vp3d_train_dropout_mask", "vp3d_train_relu_mask", "vp3d_train_layer_rows", "vp3d_train_reduce_doubles", "vp3d_adam_step", "vp3d_mpjpe_backward",
     "vp3d_seq_weight_count", "vp3d_seq_create", "vp3d_seq_destroy", "vp3d_seq_forward",
     "vp3d_seq_sliding_window",
     "vp3d_stacked_weight_count", "vp3d_stacked_create", "vp3d_stacked_forward", "vp3d_stacked_destroy",
@@ -201,6 +201,7 @@ _SIGNATURES = {
     "vp3d_train_dropout_mask": (_int, [_vp, _int, _i64, _vp, _vp]),
     "vp3d_train_relu_mask": (_int, [_vp, _int, _i64, _vp, _vp]),
     "vp3d_train_layer_rows": (_i64, [_vp, _int]),
+    "vp3d_train_reduce_doubles": (_i64, [_i64, _int, _int]),
     "vp3d_adam_step": (_int, [_int, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp),
                               ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_i64),
                               ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,

@@ -373,6 +373,13 @@ int vp3d_train_relu_mask(vp3d_trainer* t, int layer, int64_t n_elems, uint8_t* o
 /* Row count (B * frames) of conv layer `layer`'s output in the latest forward, or -1. */
 int64_t vp3d_train_layer_rows(const vp3d_trainer* t, int layer);
 
+/* Doubles of per-channel partial sums (two per channel and row chunk) of a column reduction
+ * over `rows` rows of `channels`: reserved = 0, what a reduction over exactly `rows` rows
+ * writes; reserved = 1, what a trainer sized for `rows` rows reserves, a bound over every row
+ * count up to `rows` (the chunk count is not monotone in the row count).  Host arithmetic only;
+ * test hook.  -1 for a negative row count or channels <= 0. */
+int64_t vp3d_train_reduce_doubles(int64_t rows, int channels, int reserved);
+
 /* One Adam step over n tensors (torch.optim.Adam, _single_tensor_adam; run.py:662
  * builds it with amsgrad=True): for each i, with g = grad (+ weight_decay * param),
  *   exp_avg = lerp(exp_avg, g, 1 - beta1)   (as fma, like ATen's vectorised lerp)

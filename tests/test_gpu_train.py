@@ -26,7 +26,9 @@ BN statistics in f64):
                      from the reference's own weights of step it-1 (teacher forcing), so
                      each step is compared on identical inputs.
   Adam kernel alone  exp_avg / exp_avg_sq / max_exp_avg_sq bit-exact against
-                     torch.optim.Adam (CPU); parameters within 1 ulp of the update: the f32
+                     torch.optim.Adam (CPU) on every option set of train_cases.ADAM_CASES (with
+                     weight decay: the decayed gradient is one fused multiply-add, as ATen's
+                     vectorised add(alpha=) forms it); parameters within 1 ulp of the update: the f32
                      sqrt is correctly rounded, torch-CPU's vectorised sqrt is not (errors
                      up to ~0.55 ulp measured), so ~1 % of the updates differ by 1 ulp.
 """
@@ -37,7 +39,8 @@ import numpy as np
 import pytest
 import torch
 
-from oracle.train_ref import TrainLoop, lifter_train_forward, mpjpe as mpjpe_ref
+import train_cases as TC
+from train_cases import _grad_close, _masks, _model, _oracle, _weights_close
 from vp3d_amd import synth
 from vp3d_amd.lifter import weight_order
 
@@ -52,52 +55,6 @@ def _load(name):
     g = np.load(os.path.join(GOLD, name + ".npz"), allow_pickle=False)
     meta = json.loads(str(g["meta"]))
     return g, meta, {k[2:]: g[k] for k in g.files if k.startswith("w/")}
-
-
-def _model(meta, state, dropout=0.0, channels=None, jin=17):
-    from common.models.TemporalModel import TemporalModel, TemporalModelOptimized1f
-    c = channels or meta["channels"]
-    if meta["strided"]:
-        m = TemporalModelOptimized1f(jin, 2, 17, meta["fw"], causal=meta["causal"], channels=c, dropout=dropout)
-    else:
-        m = TemporalModel(jin, 2, 17, meta["fw"], causal=meta["causal"], channels=c, dropout=dropout,
-                          dense=meta["dense"])
-    m.load_state_dict({k: torch.from_numpy(np.array(v)) for k, v in state.items()})
-    return m.cuda().train()
-
-
-def _oracle(state, x, tgt, meta, p=0.0, masks=None, dtype=torch.float32, relu_masks=None):
-    """Oracle train-mode forward + mpjpe + backward in `dtype`: (y, loss, grads, running stats)."""
-    params = {k: torch.tensor(np.array(v), dtype=dtype) for k, v in state.items()
-              if not k.endswith("num_batches_tracked")}
-    for k, t in params.items():
-        if "running" not in k:
-            t.requires_grad_(True)
-    y = lifter_train_forward(params, torch.from_numpy(np.asarray(x)).to(dtype), meta["fw"], causal=meta["causal"],
-                             strided=meta["strided"], dense=meta["dense"], p=p, masks=masks,
-                             relu_masks=relu_masks)
-    loss = mpjpe_ref(y, torch.from_numpy(np.asarray(tgt)).to(dtype))
-    loss.backward()
-    grads = {k: t.grad.numpy() for k, t in params.items() if t.requires_grad}
-    stats = {k: t.detach().numpy() for k, t in params.items() if "running" in k}
-    return y.detach().numpy(), float(loss), grads, stats
-
-
-def _grad_close(got, g32, g64, what):
-    got, g32, g64 = (np.asarray(a, dtype=np.float64) for a in (got, g32, g64))
-    nrm = max(np.linalg.norm(g64), 1e-30)
-    rel = np.linalg.norm(got - g64) / nrm
-    ref_rel = np.linalg.norm(g32 - g64) / nrm
-    err = np.abs(got - g64).max()
-    print(f"{what}: rel {rel:.2e} (oracle fp32 {ref_rel:.2e}), max|d|/max|g| {err / np.abs(g64).max():.2e}")
-    assert rel <= max(1e-4, 4 * ref_rel), f"{what}: relative error {rel:.3e} (oracle fp32 {ref_rel:.3e})"
-    assert err <= 2e-3 * np.abs(g64).max() + 1e-30, f"{what}: max|d| {err:.3e}"
-
-
-def _weights_close(got, want, lr, what):
-    d = np.abs(np.asarray(got, np.float64) - np.asarray(want, np.float64))
-    assert d.max() <= 2 * lr + 1e-6, f"{what}: {d.max():.3e}"
-    assert (d <= 1e-5).mean() >= 0.999, f"{what}: {(d > 1e-5).mean():.4%} of weights off by > 1e-5"
 
 
 @pytest.mark.parametrize("name", CASES)
@@ -149,13 +106,6 @@ def test_train_step_with_stock_torch_adam():
     for k, v in m.state_dict().items():
         if "running" not in k and not k.endswith("num_batches_tracked"):
             _weights_close(v.cpu().numpy(), g[f"s0/after/{k}"], meta["lr"], k)
-
-
-def _masks(m, B, T, kind="dropout"):
-    tr = m.native_trainer(torch.device("cuda", torch.cuda.current_device()))
-    n_layers = 1 + 2 * (len(m.filter_widths) - 1)
-    get = tr.dropout_mask if kind == "dropout" else tr.relu_mask
-    return [get(l, m.channels).cpu().numpy() for l in range(n_layers)]
 
 
 @pytest.mark.parametrize("strided,fw,B,T,channels", [
@@ -265,6 +215,48 @@ def test_adam_kernel_bitexact_vs_torch():
     assert n_diff / n_all < 0.03, n_diff / n_all
     for i in sc:
         assert float(sg[i]["step"]) == float(sc[i]["step"]) == 3.0
+
+
+@pytest.mark.parametrize("aid", TC.ADAM_IDS)
+def test_adam_options_bitexact_vs_torch(aid):
+    """torch.optim.Adam's other arguments (train_cases.ADAM_CASES: amsgrad off, weight decay with
+    and without amsgrad, beta1 <= 0.5 -- the other lerp branch --, 70 tensors -- two launches of
+    64 + 6 --, two groups with one gradient missing on the second step, so the step counts
+    diverge and one group's launch splits by step), three steps, by the rule of
+    test_adam_kernel_bitexact_vs_torch: moments bit-exact, parameters within 1 ulp of the update."""
+    from vp3d_amd.train import Adam
+    kw, init, steps, split = TC.adam_problem(aid)
+    cpu = [torch.tensor(a, requires_grad=True) for a in init]
+    gpu = [torch.nn.Parameter(torch.tensor(a).cuda()) for a in init]
+    o_cpu = torch.optim.Adam(TC.adam_groups(cpu, split), lr=1e-3, **kw)
+    o_gpu = Adam(TC.adam_groups(gpu, split), lr=1e-3, **kw)
+    keys = ["exp_avg", "exp_avg_sq"] + (["max_exp_avg_sq"] if kw.get("amsgrad") else [])
+    n_diff = n_all = 0
+    for gs in steps:
+        for c, gp, gr in zip(cpu, gpu, gs):
+            c.grad = None if gr is None else torch.tensor(gr)
+            gp.grad = None if gr is None else torch.tensor(gr).cuda()
+        o_cpu.step()
+        o_gpu.step()
+        sc, sg = o_cpu.state_dict()["state"], o_gpu.state_dict()["state"]
+        assert set(sc) == set(sg)
+        for i in sc:
+            assert set(sg[i]) == set(sc[i])
+            assert float(sg[i]["step"]) == float(sc[i]["step"])
+            for key in keys:
+                np.testing.assert_array_equal(sg[i][key].cpu().numpy(), sc[i][key].numpy(), err_msg=f"{i} {key}")
+        for c, gp in zip(cpu, gpu):
+            a, b = gp.detach().cpu().numpy(), c.detach().numpy()
+            tol = np.spacing(np.maximum(np.abs(b), np.float32(4e-3)))
+            d = np.abs(a.astype(np.float64) - b.astype(np.float64))
+            assert (d <= tol).all(), float((d / tol).max())
+            n_diff += int((d > 0).sum())
+            n_all += d.size
+            c.data.copy_(torch.from_numpy(a))  # continue from identical parameters
+    print(f"{aid}: {n_diff} of {n_all} parameter updates differ by an ulp")
+    assert n_diff / n_all < 0.03, n_diff / n_all
+    counts = sorted({float(s["step"]) for s in sg.values()})
+    assert counts == ([2.0, 3.0] if aid == "steps_diverge" else [3.0])
 
 
 def test_native_writes_bump_versions():
