@@ -158,11 +158,12 @@ __device__ unsigned long long* g_a4_trace;
 // output keeps the whole tile's K order, so the same bits as a 256 x 256 tile.
 // HNL = 2 (quarter-N, f16x3 only): 256 x 64 tiles, each wave 128 x 32, for tails of <= a
 // quarter round.
-template <typename CT, int ABL, int X3 = 0, bool GD = true, bool SPLIT = false, int HNL = 0>
+template <typename CT, int ABL, int X3 = 0, bool GD = true, bool SPLIT = false, int HNL = 0, bool IX = false>
 __global__ __launch_bounds__(256, 1) void conv_gemm_a4(ConvGemmParams p_arg) {
     constexpr bool HN = HNL > 0;
     static_assert(!HN || (GD && !SPLIT), "half-N tiles: grouped pieces, no split");
     static_assert(HNL < 2 || X3 != 0, "quarter-N tiles: the split-fp16 epilogue only");
+    static_assert(!IX || (X3 == 1 && GD && !SPLIT), "indirect windows: the split-fp16 whole / half-N / quarter-N tiles");
     constexpr int TN = GN >> HNL;  // tile channels
     constexpr int NJ = TN / 32;    // channel blocks of 16 per wave (two wave columns)
     constexpr int WP = TN / 32;    // W pieces per wave and K-tile (TN rows x 128 B, 4 waves)
@@ -262,7 +263,10 @@ __global__ __launch_bounds__(256, 1) void conv_gemm_a4(ConvGemmParams p_arg) {
         const int tile_n = wg - tile_m * ntn;
         m0 = (mt_base + tile_m) * GM;
         n0 = tile_n * TN;
-        const int srow0 = src_row(p, m0);  // m0 < M; wave-uniform
+        // m0 < M; wave-uniform.  IX (indirect windows, gemm::window_rows): an indirect operand's
+        // resource starts at the table, so every lane offset is non-negative (caller: table
+        // bytes < 2^31)
+        const int srow0 = IX && p.T_in < 0 ? 0 : src_row(p, m0);
         a_rsrc = make_rsrc((const char*)((const CT*)p.A + (int64_t)srow0 * p.lda) - kReb, 0x7FFFFFFFu);
         w_rsrc = make_rsrc((const char*)((const CT*)p.W + (int64_t)n0 * p.Kp) - kReb, 0x7FFFFFFFu);
         const int rrow0 = lres ? res_row(p, m0) : 0;
@@ -274,6 +278,26 @@ __global__ __launch_bounds__(256, 1) void conv_gemm_a4(ConvGemmParams p_arg) {
         asm volatile("" : "+v"(sln));
         launder_s(swv);
         const int spr = sln >> 3;
+        if constexpr (IX) {
+            // the A rows' windows and the rows inside them, then the windows' first rows -- back
+            // to back or through the table's bases, the 8 loads in one round trip
+            int wb[8], wr0[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const int q = GD ? 8 * swv + i : swv + 4 * i;
+                int m = m0 + 8 * q + spr;
+                m = m < p.M ? m : p.M - 1;
+                wb[i] = m / p.T_out;
+                va[i] = (uint32_t)((m - wb[i] * p.T_out) * p.stride);
+            }
+            window_rows(p.A, p.T_in, wb, wr0);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const int lci = GD ? (sln & 7) ^ (((i & 1) * 4 + (spr >> 1)) & 7) : lc;
+                const int reb = GD ? kReb - (i & 3) * 1024 : 0;
+                va[i] = (uint32_t)(((wr0[i] + (int)va[i] - srow0) * p.lda + lci * 8) * (int)sizeof(CT) + reb);
+            }
+        }
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             const int q = GD ? 8 * swv + i : swv + 4 * i;  // the piece's slot: rows 8q .. 8q + 7
@@ -282,7 +306,8 @@ __global__ __launch_bounds__(256, 1) void conv_gemm_a4(ConvGemmParams p_arg) {
             const int reb = GD ? kReb - (i & 3) * 1024 : 0;
             int m = m0 + 8 * q + spr;
             m = m < p.M ? m : p.M - 1;  // rows past M read a valid row; never stored
-            va[i] = (uint32_t)(((src_row(p, m) - srow0) * p.lda + lci * 8) * (int)sizeof(CT) + reb);
+            if constexpr (!IX)
+                va[i] = (uint32_t)(((src_row(p, m) - srow0) * p.lda + lci * 8) * (int)sizeof(CT) + reb);
             vw[i] = (uint32_t)(((8 * qw + prow) * p.Kp + lci * 8) * (int)sizeof(CT) + reb);  // W rows padded
             vr[i] = lres ? (uint32_t)(((res_row(p, m) - rrow0) * p.ldr + lci * 8) * (int)sizeof(CT) + reb) : 0u;
         }
@@ -695,14 +720,31 @@ __global__ __launch_bounds__(256, 1) void conv_gemm_a4(ConvGemmParams p_arg) {
                 asm volatile("" : "+v"(ln));
                 launder_s(wv);
                 const int pr = ln >> 3;
-                const int rrow0x = res_row(p, m0);
+                const int rrow0x = IX && p.R_T < 0 ? 0 : res_row(p, m0);  // (IX: as setup's srow0)
                 xr_rsrc = make_rsrc((const char*)((const f16*)p.R + (int64_t)rrow0x * p.ldr), 0x7FFFFFFFu);
+                if constexpr (IX) {
+                    int wb[8], wr0[8];
 #pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    int m = m0 + 8 * (8 * wv + i) + pr;
-                    m = m < p.M ? m : p.M - 1;
-                    const int lci = (ln & 7) ^ (((i & 1) * 4 + (pr >> 1)) & 7);
-                    vr[i] = (uint32_t)((res_row(p, m) - rrow0x) * p.ldr * 2 + lci * 16);
+                    for (int i = 0; i < 8; ++i) {
+                        int m = m0 + 8 * (8 * wv + i) + pr;
+                        m = m < p.M ? m : p.M - 1;
+                        wb[i] = m / p.T_out;
+                        vr[i] = (uint32_t)((m - wb[i] * p.T_out) * p.R_stride + p.R_off);
+                    }
+                    window_rows(p.R, p.R_T, wb, wr0);
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) {
+                        const int lci = (ln & 7) ^ (((i & 1) * 4 + (pr >> 1)) & 7);
+                        vr[i] = (uint32_t)((wr0[i] + (int)vr[i] - rrow0x) * p.ldr * 2 + lci * 16);
+                    }
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) {
+                        int m = m0 + 8 * (8 * wv + i) + pr;
+                        m = m < p.M ? m : p.M - 1;
+                        const int lci = (ln & 7) ^ (((i & 1) * 4 + (pr >> 1)) & 7);
+                        vr[i] = (uint32_t)((res_row(p, m) - rrow0x) * p.ldr * 2 + lci * 16);
+                    }
                 }
             };
             // piece (i, s) of quarter (hh, wcq): this wave's A-piece rows i, 128-byte group s
@@ -1019,7 +1061,7 @@ __global__ __launch_bounds__(256, 1) void conv_gemm_a4(ConvGemmParams p_arg) {
                 }
                 if (erole == kOwner) owner_wait(esidx);
                 const __amdgpu_buffer_rsrc_t y_rsrc = y_rsrc_of();
-                const int rrow0 = has_r ? res_row(p, em0) : 0;
+                const int rrow0 = has_r && !(IX && p.R_T < 0) ? res_row(p, em0) : 0;  // (IX: as setup's srow0)
                 const __amdgpu_buffer_rsrc_t rx_rsrc =
                     make_rsrc(has_r ? (const f16*)p.R + (int64_t)rrow0 * p.ldr : (const f16*)p.A, 0x7FFFFFFFu);
                 // the residual of a whole half (8 row blocks x 2 x hi / lo, 128 VGPRs) loaded up
@@ -1029,11 +1071,22 @@ __global__ __launch_bounds__(256, 1) void conv_gemm_a4(ConvGemmParams p_arg) {
                     const int nw = en0 + ewc * (TN / 2) + 64 * HH;
                     u32x4 rr[8][2][2];
                     if (has_r && !(ABL & 8)) {
+                        int wb[8], wo[8], wr0[8];
+                        if constexpr (IX) {
+#pragma unroll
+                            for (int i = 0; i < 8; ++i) {
+                                int m = em0 + ewr * 128 + 16 * i + er16;
+                                m = m < p.M ? m : p.M - 1;
+                                wb[i] = m / p.T_out;
+                                wo[i] = (m - wb[i] * p.T_out) * p.R_stride + p.R_off;
+                            }
+                            window_rows(p.R, p.R_T, wb, wr0);
+                        }
 #pragma unroll
                         for (int i = 0; i < 8; ++i) {
                             int m = em0 + ewr * 128 + 16 * i + er16;
                             m = m < p.M ? m : p.M - 1;  // valid address; rows past M are never stored
-                            const int off = ((res_row(p, m) - rrow0) * p.ldr + 2 * nw + ec0) * 2;
+                            const int off = (((IX ? wr0[i] + wo[i] : res_row(p, m)) - rrow0) * p.ldr + 2 * nw + ec0) * 2;
 #pragma unroll
                             for (int jp = 0; jp < NB / 2; ++jp) {  // (quarter-N: the wave's 32 channels only)
                                 rr[i][jp][0] = __builtin_bit_cast(
@@ -1207,6 +1260,7 @@ bool conv_gemm_a4_eligible(const ConvGemmParams& p, Act a_type, Act out_type, Ac
 
 static int a4_hn_tail(const ConvGemmParams& p, int ntiles, bool x3, int* level = nullptr);
 static bool a4_tail_split(const ConvGemmParams& p, int mt_tail, int level, bool need_ws);
+static bool a4_indirect(const ConvGemmParams& p);
 
 bool conv_gemm_a4_x3_eligible(const ConvGemmParams& p, bool out_f32) {
     if (p.Ktap % GK != 0 || p.Kp % GK != 0 || p.lda % 8 != 0) return false;
@@ -1326,6 +1380,23 @@ bool conv_gemm_a4_would_split(const ConvGemmParams& p) {
     return q.sk_split > 1;
 }
 
+static bool a4_indirect(const ConvGemmParams& p) { return p.T_in < 0 || (p.R != nullptr && p.R_T < 0); }
+
+// an f16x3 layer with indirect windows (T_in < 0 / R_T < 0, gemm::window_rows) runs on a4 when its
+// launch is whole tiles with a half-N / quarter-N tail at most: the split-K plans and the
+// split-K tail (conv_gemm_tail.hip) address their rows themselves
+bool conv_gemm_a4_x3_indirect_ok(const ConvGemmParams& p) {
+    if (!conv_gemm_a4_x3_eligible(p, false)) return false;
+    const int ntiles = ((p.M + GM - 1) / GM) * (p.N / GN);
+    const char* we = getenv("VP3D_A4_WALK");
+    int level = 1;
+    const int hn = we && atoi(we) == 2 ? 0 : a4_hn_tail(p, ntiles, true, &level);
+    if (hn > 0) return !a4_tail_split(p, hn, level, false);
+    ConvGemmParams q = p;
+    a4_split_plan(q, ntiles, p.Kp / GK, false);
+    return q.sk_split <= 1;
+}
+
 bool conv_gemm_a4_fills(const ConvGemmParams& p) {
     const int ntiles = ((p.M + GM - 1) / GM) * (p.N / GN);
     if (ntiles >= 384) return true;
@@ -1335,9 +1406,11 @@ bool conv_gemm_a4_fills(const ConvGemmParams& p) {
     return q.sk_split > 1;
 }
 
-template <typename CT, int X3>
+template <typename CT, int X3, bool IX = false>
 static void a4_launch(const ConvGemmParams& p, dim3 grid, bool split, hipStream_t stream) {
-    if (split)
+    if constexpr (IX)  // (indirect windows: never split, launch_conv_gemm_a4_x3)
+        hipLaunchKernelGGL((conv_gemm_a4<CT, 0, X3, true, false, 0, true>), grid, dim3(256), 0, stream, p);
+    else if (split)
         hipLaunchKernelGGL((conv_gemm_a4<CT, 0, X3, true, true>), grid, dim3(256), 0, stream, p);
     else
         hipLaunchKernelGGL((conv_gemm_a4<CT, 0, X3, true, false>), grid, dim3(256), 0, stream, p);
@@ -1345,7 +1418,7 @@ static void a4_launch(const ConvGemmParams& p, dim3 grid, bool split, hipStream_
 
 // the whole rounds (M-tiles below ntm - mt_tail, if any; walked by one workgroup per CU when
 // `walk_cus` > 0) then the tail as half-N units
-template <typename CT, int X3>
+template <typename CT, int X3, bool IX = false>
 static void a4_launch_whole(const ConvGemmParams& p, int mt0, hipStream_t stream, int walk_cus) {
     if (mt0 > 0) {
         ConvGemmParams q = p;
@@ -1353,26 +1426,26 @@ static void a4_launch_whole(const ConvGemmParams& p, int mt0, hipStream_t stream
         q.sk_split = q.sk_full = q.sk_left = 0;
         const int tiles = mt0 * (p.N / GN);
         const dim3 g(walk_cus > 0 && tiles > walk_cus ? walk_cus : tiles);
-        hipLaunchKernelGGL((conv_gemm_a4<CT, 0, X3, true, false>), g, dim3(256), 0, stream, q);
+        hipLaunchKernelGGL((conv_gemm_a4<CT, 0, X3, true, false, 0, IX>), g, dim3(256), 0, stream, q);
     }
 }
 
-template <typename CT, int X3>
+template <typename CT, int X3, bool IX = false>
 static void a4_launch_hn(const ConvGemmParams& p, int mt_tail, hipStream_t stream, int walk_cus = 0, int level = 1) {
     const int ntm = (p.M + GM - 1) / GM;
     const int mt0 = ntm - mt_tail;
-    a4_launch_whole<CT, X3>(p, mt0, stream, walk_cus);
+    a4_launch_whole<CT, X3, IX>(p, mt0, stream, walk_cus);
     ConvGemmParams t = p;
     t.sk_split = t.sk_left = 0;
     t.sk_full = mt0;  // the HN launch's first M-tile
     if constexpr (X3 != 0) {
         if (level == 2) {
-            hipLaunchKernelGGL((conv_gemm_a4<CT, 0, X3, true, false, 2>), dim3(mt_tail * (p.N / (GN / 4))), dim3(256),
+            hipLaunchKernelGGL((conv_gemm_a4<CT, 0, X3, true, false, 2, IX>), dim3(mt_tail * (p.N / (GN / 4))), dim3(256),
                                0, stream, t);
             return;
         }
     }
-    hipLaunchKernelGGL((conv_gemm_a4<CT, 0, X3, true, false, 1>), dim3(mt_tail * (p.N / (GN / 2))), dim3(256), 0,
+    hipLaunchKernelGGL((conv_gemm_a4<CT, 0, X3, true, false, 1, IX>), dim3(mt_tail * (p.N / (GN / 2))), dim3(256), 0,
                        stream, t);
 }
 
@@ -1394,10 +1467,18 @@ hipError_t launch_conv_gemm_a4_x3(const ConvGemmParams& p_in, bool out_f32, hipS
     const int walk_mode = we ? atoi(we) : 1;
     int hn_level = 1;
     const int hn_tail = walk_mode == 2 ? 0 : a4_hn_tail(p, ntiles, true, &hn_level);
+    // indirect windows (gemm::window_rows; the caller asked conv_gemm_a4_x3_indirect_ok): the
+    // whole, half-N and quarter-N tiles of the split rows form only
+    const bool ix = a4_indirect(p);
+    if (ix && (out_f32 || !conv_gemm_a4_x3_indirect_ok(p))) return hipErrorInvalidValue;
 #ifndef VP3D_ABLATION
     if (hn_tail > 0) {
         // the whole rounds walked as without the tail (the 1x1 + residual layers)
         const int wc = walk_mode > 0 && p.R != nullptr ? a4_cus() : 0;
+        if (ix) {
+            a4_launch_hn<_Float16, 1, true>(p, hn_tail, stream, wc, hn_level);
+            return hipGetLastError();
+        }
         if (a4_tail_split(p, hn_tail, hn_level, true)) {
             // a tail of <= a quarter round after whole rounds (sequence mode): split over every
             // CU in its K range too (conv_gemm_tail.hip), not as 4L quarter-N full-K chains
@@ -1440,7 +1521,9 @@ hipError_t launch_conv_gemm_a4_x3(const ConvGemmParams& p_in, bool out_f32, hipS
         return hipGetLastError();
     }
 #endif
-    if (out_f32)
+    if (ix)
+        a4_launch<_Float16, 1, true>(p, grid, false, stream);
+    else if (out_f32)
         a4_launch<_Float16, 2>(p, grid, split, stream);
     else
         a4_launch<_Float16, 1>(p, grid, split, stream);

@@ -1,0 +1,88 @@
+// The expand table's two small kernels (vp3d_capi.cpp, forward_impl's table path).
+//
+// The expand conv's output row is a function of (sequence, frame position) alone, so an f16x3
+// forward of many windows over few resident frames computes it once per frame into a table --
+// row j of sequence i = the expand output for unclamped frames lo + j - lead .. + taps - 1,
+// T_tab rows per sequence -- and the block-1 convs read window b's row t at table row
+// base[b] + t * s0 (s0 = the expand conv's frame stride).  The table spans the starts
+// lo = -(span + ...) .. len - 1 + lead + span (span = the rows a window steps over): a window
+// starting before `lo` has only rows whose frames all clamp to frame 0, as the window starting
+// at `lo` has, and one starting past len - 1 + lead only rows of the last frame, as the window
+// starting there -- so clamping the start into that range reproduces the per-frame edge clamp
+// (generators.py:92-100) for every start.
+//   window_bases        base[b] = seq_b * T_tab + clamp(start_b) - lo; a sequence outside the
+//                       pool is a fault
+//   gather_table_rows   the windows' rows copied out of the table into the contiguous
+//                       (B, T_out) layout the expand conv itself writes (kernel forms without
+//                       indirect windows; the bit-identity reference of the tests)
+#include "kernels.h"
+
+namespace vp3d {
+namespace {
+
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+
+__global__ __launch_bounds__(256) void window_bases_kernel(const int32_t* __restrict__ pairs,
+                                                           const int32_t* __restrict__ seq_len, int B, int n_seq,
+                                                           int T_tab, int lo, int lead, int32_t* __restrict__ base,
+                                                           unsigned* fault) {
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= B) return;
+    const int2 pr = *(const int2*)(pairs + 2 * b);
+    // a sequence outside the pool has no table rows: fault, and a base inside the table so that
+    // the convs read valid rows
+    const bool ok = pr.x >= 0 && pr.x < n_seq;
+    const int hi = seq_len[ok ? pr.x : 0] - 1 + lead;  // (>= lo: lo <= 0, len >= 1, lead >= 0)
+    const int st = pr.y < lo ? lo : (pr.y > hi ? hi : pr.y);
+    base[b] = ok ? pr.x * T_tab + (st - lo) : 0;
+    if (!ok && fault) __hip_atomic_fetch_or(fault, kFaultWindowStart, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// out row (b, t) = table row base[b] + t * s0; rows of `row16` 16-byte words, one word per lane,
+// kRowsPerWg rows per workgroup trip
+template <bool NT>
+__global__ __launch_bounds__(256) void gather_table_rows_kernel(const u32x4* __restrict__ table,
+                                                                const int32_t* __restrict__ base, int64_t rows,
+                                                                int T_out, int s0, int row16, u32x4* __restrict__ out) {
+    for (int64_t r = blockIdx.x; r < rows; r += gridDim.x) {
+        const int b = (int)(r / T_out);
+        const int t = (int)(r - (int64_t)b * T_out);
+        const u32x4* src = table + (int64_t)(base[b] + t * s0) * row16;
+        u32x4* dst = out + r * row16;
+        for (int c = threadIdx.x; c < row16; c += 256) {
+            const u32x4 v = src[c];
+            if (NT)
+                __builtin_nontemporal_store(v, dst + c);
+            else
+                dst[c] = v;
+        }
+    }
+}
+
+}  // namespace
+
+hipError_t launch_window_bases(const int32_t* pairs, const int32_t* seq_len, int B, int n_seq, int T_tab, int lo,
+                               int lead, int32_t* base, unsigned* fault, hipStream_t s) {
+    if (lo > 0 || lead < 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(window_bases_kernel, dim3((B + 255) / 256), dim3(256), 0, s, pairs, seq_len, B, n_seq, T_tab,
+                       lo, lead, base, fault);
+    return hipGetLastError();
+}
+
+hipError_t launch_gather_table_rows(const void* table, const int32_t* base, int B, int T_out, int s0,
+                                    int row_bytes, void* out, hipStream_t s) {
+    if (row_bytes % 16 != 0 || B <= 0 || T_out <= 0) return hipErrorInvalidValue;
+    const int64_t rows = (int64_t)B * T_out;
+    // nontemporal above the 256 MB Infinity Cache, as the expand conv's own stores (expand_gemm.hip)
+    const bool nt = rows * row_bytes > (int64_t)256 << 20;
+    const unsigned grid = (unsigned)(rows < (1 << 20) ? rows : (1 << 20));
+    if (nt)
+        hipLaunchKernelGGL(gather_table_rows_kernel<true>, dim3(grid), dim3(256), 0, s, (const u32x4*)table, base, rows,
+                           T_out, s0, row_bytes / 16, (u32x4*)out);
+    else
+        hipLaunchKernelGGL(gather_table_rows_kernel<false>, dim3(grid), dim3(256), 0, s, (const u32x4*)table, base, rows,
+                           T_out, s0, row_bytes / 16, (u32x4*)out);
+    return hipGetLastError();
+}
+
+}  // namespace vp3d

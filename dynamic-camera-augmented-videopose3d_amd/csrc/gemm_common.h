@@ -67,8 +67,32 @@ __device__ __forceinline__ int res_row(const ConvGemmParams& p, int m) {
     return b * p.R_T + t * p.R_stride + p.R_off;
 }
 
+// Indirect windows (conv_gemm_a4; the expand table of vp3d_capi.cpp): an operand whose window
+// pitch T (ConvGemmParams::T_in for A, R_T for the split-fp16 residual) is negative holds its
+// windows at arbitrary rows of one shared table -- window b starts at row base[b], base = the
+// int32 vector at (const int*)operand + T, i.e. |T| ints in front of the table -- instead of
+// back to back at b * T.  window_rows gives the first row of N windows either way.  The loaded
+// bases are consumed inside the branch, so the wait for them sits there and a direct operand
+// never waits on vmcnt here (a walked kernel runs this ahead of its epilogue's stores).
+template <int N>
+__device__ __forceinline__ void window_rows(const void* op, int T, const int (&b)[N], int (&r0)[N]) {
+    if (T < 0) {
+        // (global address space spelled out: a pointer that went through an empty asm is a
+        // generic one to the compiler, and a flat load counts on lgkmcnt as well)
+        typedef const __attribute__((address_space(1))) int* gbl_int_ptr;
+        const gbl_int_ptr base = (gbl_int_ptr)op + T;
+#pragma unroll
+        for (int i = 0; i < N; ++i) r0[i] = base[b[i]];
+#pragma unroll
+        for (int i = 0; i < N; ++i) asm volatile("" : "+v"(r0[i]));
+    } else {
+#pragma unroll
+        for (int i = 0; i < N; ++i) r0[i] = b[i] * T;
+    }
+}
+
 // A-operand addressing modes
-//   A_SCALAR  general tap mapping, one element at a time (bounds-checked, zero fill)
+//   A_SCALAR general tap mapping, one element at a time (bounds-checked, zero fill)
 //   A_PAIRS   one contiguous K segment per row (taps collapsed, dil == 1) of f32
 //             activations with an even row pitch: 8-byte loads, no division
 //             (the expand conv: K = w0 * J * F = 102 or 138)

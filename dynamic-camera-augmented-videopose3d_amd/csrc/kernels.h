@@ -97,6 +97,12 @@ hipError_t launch_conv_gemm_a4(const ConvGemmParams& p, Act compute, hipStream_t
 // bits as conv_gemm_q64_x3.
 bool conv_gemm_a4_x3_eligible(const ConvGemmParams& p, bool out_f32);
 hipError_t launch_conv_gemm_a4_x3(const ConvGemmParams& p, bool out_f32, hipStream_t stream);
+// Indirect windows (the expand table, vp3d_capi.cpp): with T_in < 0 the A operand's window b
+// starts at row base[b] of one shared table, base = (const int*)A + T_in (|T_in| ints in front
+// of the table), instead of at b * T_in; R_T < 0 likewise for the split residual.  Table bytes
+// < 2^31 - 64 KiB (32-bit lane offsets from the table start).  Taken by launch_conv_gemm_a4_x3
+// (split output) where this holds: whole tiles with a half-N / quarter-N tail at most.
+bool conv_gemm_a4_x3_indirect_ok(const ConvGemmParams& p);
 // Split-K tail of an a4 launch (conv_gemm_tail.hip): rows [m_begin, M) as (N / 64) x S
 // K-slices of 256 x 64 over `ncu` CUs, f32 partials in p.sk_part (the split workspace), then
 // one reduction launch with a4's epilogue -- the split-fp16 one (x3) or the 16-bit one (bf16 /
@@ -350,6 +356,15 @@ constexpr unsigned kFaultSplitTimeout = 1u;   // a split-K owner gave up waiting
 // an f16x3 forward split a value past the f16 range (|x| > 65,504, gemm::x3_range_flag) or
 // produced a non-finite pose value
 constexpr unsigned kFaultNonFinite = 2u;
+// a window of a table-mode forward (expand_table.hip) named a sequence outside the pool
+constexpr unsigned kFaultWindowStart = 4u;
+// expand_table.hip: the table path of an f16x3 vp3d_forward_windows_pool (vp3d_capi.cpp)
+// base[b] = seq_b * T_tab + clamp(start_b, lo, seq_len - 1 + lead) - lo (table row 0 of a
+// sequence = start `lo`)
+hipError_t launch_window_bases(const int32_t* pairs, const int32_t* seq_len, int B, int n_seq, int T_tab, int lo,
+                               int lead, int32_t* base, unsigned* fault, hipStream_t s);
+hipError_t launch_gather_table_rows(const void* table, const int32_t* base, int B, int T_out, int s0,
+                                    int row_bytes, void* out, hipStream_t s);
 hipError_t launch_pose_metrics(const float* pred, const float* target, int64_t n_frames, int J, double* acc,
                                hipStream_t s);
 

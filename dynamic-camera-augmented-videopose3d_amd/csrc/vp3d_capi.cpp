@@ -394,10 +394,12 @@ bool layer_lengths(const vp3d_handle* h, int T, std::vector<int>& len) {
 // bytes per activation element: f32, one 16-bit value, or a split-fp16 (hi, lo) pair
 size_t esize(int dtype) { return dtype == VP3D_DTYPE_F32 || dtype == VP3D_DTYPE_F16X3 ? 4 : 2; }
 
-int ensure_ws(vp3d_handle* h, int B, int T, int dtype) {
+// `first`: the first layer whose output lives in the rotating buffers (1 when the expand conv
+// writes the expand table instead, forward_impl's table path)
+int ensure_ws(vp3d_handle* h, int B, int T, int dtype, int first = 0) {
     std::vector<int> len;
     if (!layer_lengths(h, T, len)) return fail(VP3D_ERR_ARG, "input too short for the receptive field");
-    const size_t rows = (size_t)B * len[0];
+    const size_t rows = (size_t)B * len[first];
     // three rotating activation buffers + (16-bit path) the packed expand-conv rows
     const size_t need = 3 * rows * h->cfg.channels * esize(dtype) +
                         (dtype == VP3D_DTYPE_F32 ? 0 : rows * h->layers[0].Kp * (dtype == VP3D_DTYPE_F16X3 ? 4 : 2));
@@ -485,7 +487,130 @@ constexpr const char* kNonFiniteMsg =
     "65504) or produced non-finite poses; its outputs are not valid -- run those inputs in fp32 "
     "(with an activation pre-scale set: re-calibrate with more headroom or clear the pre-scale). "
     "vp3d_sync_status clears the fault";
-const char* fault_msg(unsigned w) { return (w & vp3d::kFaultSplitTimeout) ? kSplitFaultMsg : kNonFiniteMsg; }
+constexpr const char* kWindowStartMsg =
+    "f16x3 expand table: an earlier forward on this handle had a window that names a sequence outside "
+    "the pool, [0, n_seq); its outputs are not valid. vp3d_sync_status clears the fault";
+const char* fault_msg(unsigned w) {
+    if (w & vp3d::kFaultSplitTimeout) return kSplitFaultMsg;
+    return (w & vp3d::kFaultWindowStart) && !(w & vp3d::kFaultNonFinite) ? kWindowStartMsg : kNonFiniteMsg;
+}
+
+// The expand table (expand_table.hip): whether an f16x3 gathered forward computes the expand conv
+// once per resident frame, and how block 1 reads it.  Decided from sizes (and VP3D_EXPAND_TABLE,
+// read here once per forward) alone.
+struct TablePlan {
+    int mode = 0;   // 0: the expand conv per window row; 1: block 1 reads the table through
+                    // indirect windows (conv_gemm_a4); 2: the windows' rows copied out of it
+    int T_tab = 0;  // table rows per sequence
+    int lo = 0;     // the window start table row 0 of a sequence stands for (<= 0, expand_table.hip)
+    int s0 = 1;     // table rows between consecutive rows of a window (the expand conv's stride)
+    int b_pad = 0;  // int32 slots of the window bases in front of the table
+    size_t table_bytes = 0;
+    bool forced = false;  // VP3D_EXPAND_TABLE=1 / copy
+};
+// table rows may number at most 1 / kTableFactor of the window rows they replace
+constexpr int kTableFactor = 2;
+
+TablePlan plan_expand_table(const vp3d_handle* h, int B, const std::vector<int>& len, int dtype, const GatherSrc* gs,
+                            int n_seq, int max_len) {
+    TablePlan tp;
+    const int nl = (int)h->layers.size();
+    if (dtype != VP3D_DTYPE_F16X3 || !gs || gs->cams || n_seq <= 0 || max_len <= 0 || nl < 4) return tp;
+    const char* e = getenv("VP3D_EXPAND_TABLE");
+    if (e && e[0] == '0') return tp;
+    const bool force = e && (strcmp(e, "1") == 0 || strcmp(e, "copy") == 0);
+    const Layer& L0 = h->layers[0];
+    const int C = L0.cout;
+    tp.s0 = L0.stride;
+    // starts lo .. max_len - 1 + lead, then the rows a window steps over (expand_table.hip: every
+    // start clamps into that range with the per-frame edge clamp's result)
+    if (gs->lead < 0) return tp;
+    const int64_t span = (int64_t)(len[0] - 1) * tp.s0;
+    tp.lo = -(int)(span + std::max(0, L0.taps - 1 - gs->lead));
+    const int64_t t_tab = ((int64_t)max_len - 1 + gs->lead - tp.lo + span + 1 + 15) / 16 * 16;
+    const int64_t rows = (int64_t)n_seq * t_tab;
+    const int64_t bytes = rows * 2 * C * 2;
+    // 32-bit lane offsets from the table start (conv_gemm_a4), some slack for the tiles' rebased
+    // resources; one rule for both table modes
+    if (bytes >= ((int64_t)1 << 31) - 65536) return tp;
+    if (!force && rows > (int64_t)B * len[0] / kTableFactor) return tp;
+    tp.T_tab = (int)t_tab;
+    tp.table_bytes = (size_t)bytes;
+    tp.b_pad = (B + 63) / 64 * 64;
+    tp.mode = 2;
+    tp.forced = force;
+    if (e && strcmp(e, "copy") == 0) return tp;
+    // indirect windows where both block-1 convs run the a4 tile forms that take them (the
+    // pointers only stand for their alignment here)
+    const char* ge = getenv("VP3D_GEMM");
+    if (ge && strcmp(ge, "q64") == 0) return tp;
+    if (nl - 2 == 2 && !x3_split_shrink(h)) return tp;  // (the 1x1 would write f32 rows)
+    void* const al = (void*)(uintptr_t)256;
+    const Layer &L1 = h->layers[1], &L2 = h->layers[2];
+    ConvGemmParams q{};
+    q.A = q.W = al;
+    q.Y = al;
+    q.M = B * len[1];
+    q.N = L1.cout;
+    q.K = L1.K;
+    q.Kp = 2 * L1.Kp;
+    q.T_out = len[1];
+    q.T_in = -tp.b_pad;
+    q.stride = L1.stride * tp.s0;
+    q.dil = L1.dil * tp.s0;
+    q.Ktap = 2 * L1.cin;
+    q.lda = 2 * L1.cin;
+    q.ldy = 2 * L1.cout;
+    q.relu = 1;
+    if (!L1.relu || L1.residual || !vp3d::conv_gemm_a4_x3_indirect_ok(q)) return tp;
+    ConvGemmParams r{};
+    r.A = r.W = al;
+    r.Y = al;
+    r.R = al;
+    r.M = B * len[2];
+    r.N = L2.cout;
+    r.K = L2.K;
+    r.Kp = 2 * L2.Kp;
+    r.T_out = len[2];
+    r.T_in = len[1];
+    r.stride = L2.stride;
+    r.dil = L2.dil;
+    r.Ktap = 2 * L2.Ktap;
+    r.lda = 2 * L2.cin;
+    r.ldy = 2 * L2.cout;
+    r.ldr = 2 * L2.cout;
+    r.R_T = -tp.b_pad;
+    r.relu = 1;
+    if (!L2.relu || !L2.residual || !vp3d::conv_gemm_a4_x3_indirect_ok(r)) return tp;
+    tp.mode = 1;
+    return tp;
+}
+
+// the table allocation ([bases | table]) and the table's own pair list
+int ensure_table(vp3d_handle* h, const TablePlan& tp, int n_seq, hipStream_t s) {
+    const bool same_pairs = (int)h->tab_pairs_host.size() == 2 * n_seq && (n_seq == 0 || h->tab_pairs_host[1] == tp.lo);
+    const size_t need = (size_t)tp.b_pad * 4 + tp.table_bytes;
+    if (need > h->tab_bytes) {
+        if (h->tab_ws) HIP_TRY(hipFree(h->tab_ws));
+        h->tab_ws = nullptr;
+        h->tab_bytes = 0;
+        HIP_TRY(hipMalloc(&h->tab_ws, need));
+        h->tab_bytes = need;
+    }
+    if (!same_pairs) {
+        // (the device synchronised by the free: the host list is no copy's source any more)
+        if (h->tab_pairs) HIP_TRY(hipFree(h->tab_pairs));
+        h->tab_pairs = nullptr;
+        h->tab_pairs_host.assign((size_t)2 * n_seq, 0);
+        for (int i = 0; i < n_seq; ++i) {
+            h->tab_pairs_host[2 * i] = i;
+            h->tab_pairs_host[2 * i + 1] = tp.lo;
+        }
+        HIP_TRY(hipMalloc((void**)&h->tab_pairs, (size_t)2 * n_seq * 4));
+        HIP_TRY(hipMemcpyAsync(h->tab_pairs, h->tab_pairs_host.data(), (size_t)2 * n_seq * 4, hipMemcpyHostToDevice, s));
+    }
+    return VP3D_OK;
+}
 
 hipEvent_t get_event(vp3d_handle* h) {
     if (!h->free_events.empty()) {
@@ -553,6 +678,8 @@ int vp3d_destroy(vp3d_handle* h) {
     free_layers(h);
     if (h->ws) hipFree(h->ws);
     if (h->gather_ws) hipFree(h->gather_ws);
+    if (h->tab_ws) hipFree(h->tab_ws);
+    if (h->tab_pairs) hipFree(h->tab_pairs);
     if (h->sk_ws) hipFree(h->sk_ws);
     if (h->x3_stats) hipFree(h->x3_stats);
     if (h->sk_err_host) hipHostFree(h->sk_err_host);
@@ -607,8 +734,10 @@ int vp3d_reserve(vp3d_handle* h, int B, int T, int dtype) {
 // describing where the windows are gathered from (vp3d_forward_windows).
 // `calib` (fp32 only): per-layer device accumulators of the calibration pass; every conv
 // layer's f32 output rows (not the shrink's poses) are reduced into calib[layer] after its launch.
+// n_seq / max_len (vp3d_forward_windows_pool): the sequences `gs` may refer to and the longest
+// one's length -- what the expand table path (plan_expand_table) is decided and sized from.
 static int forward_impl(vp3d_handle* h, const float* x, int B, int T, float* y, int dtype, void* stream,
-                        const GatherSrc* gs, vp3d::ActStats* calib = nullptr) {
+                        const GatherSrc* gs, vp3d::ActStats* calib = nullptr, int n_seq = 0, int max_len = 0) {
     int dev = 0;
     hipGetDevice(&dev);
     if (dev != h->device) return fail(VP3D_ERR_STATE, "handle belongs to another device");
@@ -629,15 +758,56 @@ static int forward_impl(vp3d_handle* h, const float* x, int B, int T, float* y, 
         if ((fw & vp3d::kFaultSplitTimeout) || (fw && dtype == VP3D_DTYPE_F16X3))
             return fail(VP3D_ERR_STATE, fault_msg(fw));
     }
-    int rc = ensure_ws(h, B, T, dtype);
+    const bool x3 = dtype == VP3D_DTYPE_F16X3;
+    if (x3 && !x3_supported(h)) return fail(VP3D_ERR_ARG, x3_requirement());
+    // the expand table path (f16x3, gathered, sizes only); with indirect windows the expand
+    // output never exists per window, so the buffers hold block 1's rows at most
+    TablePlan tp = plan_expand_table(h, B, len, dtype, gs, n_seq, max_len);
+    // the copy form costs more than the expand conv it replaces (it writes the same rows after
+    // filling the table): only on request, never as the automatic choice
+    if (tp.mode == 2 && !tp.forced) tp = TablePlan{};
+    GatherSrc tab_gs;
+    ConvGemmParams tab_p{};
+    if (tp.mode) {
+        // the table's fill: the expand launch itself over one pseudo-window (i, lo) of T_tab rows
+        // at frame stride 1 per sequence
+        const Layer& L0 = h->layers[0];
+        tab_gs = *gs;
+        tab_p.M = n_seq * tp.T_tab;
+        tab_p.N = L0.cout;
+        tab_p.K = L0.K;
+        tab_p.Kp = 2 * L0.Kp;
+        tab_p.T_out = tp.T_tab;
+        tab_p.T_in = T;
+        tab_p.stride = 1;
+        tab_p.dil = L0.dil;
+        tab_p.Ktap = L0.Ktap;
+        tab_p.lda = L0.cin;
+        tab_p.relu = L0.relu ? 1 : 0;
+        tab_p.ldy = 2 * L0.cout;
+        tab_p.W = L0.wx3;
+        tab_p.scale = L0.scale_x3;
+        tab_p.shift = L0.shift_x3;
+        tab_p.Y = (void*)(uintptr_t)256;  // (its alignment: the table is placed below)
+        const char* xe = getenv("VP3D_X3_EXPAND");
+        if ((xe && strcmp(xe, "pack") == 0) || !expand_gemm_x3_eligible(tab_p, &tab_gs)) tp = TablePlan{};
+    }
+    if (gs) h->tab_mode = tp.mode;
+    const int buf_first = tp.mode == 1 ? 1 : 0;
+    int rc = ensure_ws(h, B, T, dtype, buf_first);
     if (rc) return rc;
 
     hipStream_t s = (hipStream_t)stream;
-    const bool x3 = dtype == VP3D_DTYPE_F16X3;
-    if (x3 && !x3_supported(h)) return fail(VP3D_ERR_ARG, x3_requirement());
+    char* table = nullptr;
+    if (tp.mode) {
+        if ((rc = ensure_table(h, tp, n_seq, s))) return rc;
+        table = (char*)h->tab_ws + (size_t)tp.b_pad * 4;
+        tab_gs.pairs = h->tab_pairs;
+        tab_p.Y = table;
+    }
     const Act act = dtype == VP3D_DTYPE_F32 ? Act::F32 : (dtype == VP3D_DTYPE_BF16 ? Act::BF16 : Act::F16);
     const size_t es = esize(dtype);
-    const size_t buf_elems = (size_t)B * len[0] * h->cfg.channels;
+    const size_t buf_elems = (size_t)B * len[buf_first] * h->cfg.channels;
     char* base = (char*)h->ws;
     void* buf[3] = {base, base + buf_elems * es, base + 2 * buf_elems * es};
 
@@ -722,6 +892,18 @@ static int forward_impl(vp3d_handle* h, const float* x, int B, int T, float* y, 
             p.scale = L.scale_x3_f32;
             e = launch_conv_gemm(p, Act::F32, Act::F32, Act::F32, s);
             launched = true;
+        } else if (x3 && first && tp.mode) {
+            // expand table: the expand conv once per resident frame, the windows' bases, then
+            // either nothing more (block 1 reads the table through them) or the windows' rows
+            // copied out into the layout the per-window expand writes
+            e = launch_expand_gemm_x3(tab_p, &tab_gs, s);
+            if (e == hipSuccess)
+                e = launch_window_bases(gs->pairs, gs->seq_len, B, n_seq, tp.T_tab, tp.lo, gs->lead, (int32_t*)h->tab_ws,
+                                        h->sk_err_dev, s);
+            if (e == hipSuccess && tp.mode == 2)
+                e = launch_gather_table_rows(table, (const int32_t*)h->tab_ws, B, len[0], tp.s0, 2 * L.cout * 2, p.Y, s);
+            if (tp.mode == 1) p.Y = table;  // (the next layers' input; out_buf stays free)
+            launched = true;
         } else if (x3 && first && nl > 2 && [&] {
                        // VP3D_X3_EXPAND=pack (measurement): the pack + GEMM form instead
                        const char* xe = getenv("VP3D_X3_EXPAND");
@@ -758,12 +940,26 @@ static int forward_impl(vp3d_handle* h, const float* x, int B, int T, float* y, 
                 p.lda = 2 * L.cin;
                 p.Ktap = 2 * L.Ktap;
             }
+            if (tp.mode == 1 && li == 1) {
+                // block 1's k-conv over the table: window b's input row j is table row
+                // base[b] + j s0, so tap k of output row r sits at base[b] + (r stride + k dil) s0
+                // -- every tap its own K segment, the K order unchanged
+                p.T_in = -tp.b_pad;
+                p.stride = L.stride * tp.s0;
+                p.dil = L.dil * tp.s0;
+                p.Ktap = 2 * L.cin;
+            }
             const bool out_f32 = li == nl - 2 && !x3_split_shrink(h);
             p.Kp = 2 * L.Kp;
             p.W = L.wx3;
             p.scale = L.scale_x3;
             p.ldy = out_f32 ? L.cout : 2 * L.cout;
             if (L.residual) p.ldr = 2 * L.cout;
+            if (tp.mode == 1 && li == 2) {  // block 1's residual slice, out of the table
+                p.R_T = -tp.b_pad;
+                p.R_stride = L.res_stride * tp.s0;
+                p.R_off = L.res_off * tp.s0;
+            }
             // the one-wave-per-SIMD kernel where it fills the chip (VP3D_GEMM=q64 forces q64)
             const char* ge = getenv("VP3D_GEMM");
             if ((rc = attach_split_ws(h, p, s))) return rc;
@@ -892,6 +1088,33 @@ int vp3d_forward_windows(vp3d_handle* h, const float* kps, int32_t f2, const flo
     g.lead = lead;
     return forward_impl(h, nullptr, B, window, y, dtype, stream, &g);
 }
+
+int vp3d_forward_windows_pool(vp3d_handle* h, const float* kps, int32_t f2, const float* cams, const int64_t* seq_off,
+                              const int32_t* seq_len, int32_t n_seq, int32_t max_len, const int32_t* pairs, int B,
+                              int window, int lead, float* y, int dtype, void* stream) {
+    if (!h) return fail(VP3D_ERR_ARG, "handle is NULL");
+    if (!kps || !seq_off || !seq_len || !pairs || !y) return fail(VP3D_ERR_ARG, "a device pointer is NULL");
+    if (B <= 0) return fail(VP3D_ERR_ASSERT, "batch must be positive");
+    if (n_seq <= 0 || max_len <= 0) return fail(VP3D_ERR_ARG, "n_seq and max_len must be positive");
+    if (dtype < 0 || dtype > VP3D_DTYPE_F16X3) return fail(VP3D_ERR_ARG, "unknown dtype");
+    if (cams && dtype == VP3D_DTYPE_BF16)
+        return fail(VP3D_ERR_ARG, "bf16 is refused with the camera concat (use fp16, f16x3 or fp32)");
+    const int cin = h->cfg.num_joints_in * h->cfg.in_features;
+    if (f2 + (cams ? 12 : 0) != cin)
+        return fail(VP3D_ERR_ASSERT, "frame features (" + std::to_string(f2) + (cams ? " + 12" : "") +
+                                         ") != num_joints_in * in_features (" + std::to_string(cin) + ")");
+    GatherSrc g;
+    g.kps = kps;
+    g.f2 = f2;
+    g.cams = cams;
+    g.seq_off = seq_off;
+    g.seq_len = seq_len;
+    g.pairs = pairs;
+    g.lead = lead;
+    return forward_impl(h, nullptr, B, window, y, dtype, stream, &g, nullptr, n_seq, max_len);
+}
+
+int vp3d_expand_table_mode(const vp3d_handle* h) { return h ? h->tab_mode : -1; }
 
 int vp3d_sync_status(vp3d_handle* h, void* stream) {
     if (!h) return fail(VP3D_ERR_ARG, "handle is NULL");

@@ -110,8 +110,18 @@ class NativeLifter:
         """Forward of windows gathered on the fly from `seqs` (a pipeline.DeviceSequences):
         window b = frames [start_b - lead, start_b - lead + window) of sequence seq_b,
         edge-clamped; with concat_cams the 12 K.E channels follow each frame's keypoints
-        (vp3d_forward_windows: ChunkedGenerator batch + camera concat + TemporalModel forward,
-        the gather fused into the expand conv on the 16-bit path)."""
+        (vp3d_forward_windows_pool: ChunkedGenerator batch + camera concat + TemporalModel forward,
+        the gather fused into the expand conv on the 16-bit path).
+
+        `seqs` also tells the library how many sequences are resident and how long the longest
+        is.  An f16x3 forward without the camera concat whose windows outnumber the resident
+        frames (table rows <= half the window rows, table < 2 GiB: large evaluation batches)
+        then computes the expand conv once per resident frame into a table that block 1 reads
+        through per-window row bases: the same poses, bit for bit.  On that path the f16x3
+        range guard sees every resident frame of `seqs`, and a pair naming a sequence outside
+        `seqs` is a fault (RuntimeError at the next forward or sync_status); starts outside their
+        sequence are edge-clamped as on every path.  VP3D_EXPAND_TABLE=0 keeps the per-window expand; expand_table_mode() tells
+        which path the last call took."""
         def _idx(d):
             d = torch.device(d)
             return (d.type, d.index if d.index is not None else torch.cuda.current_device())
@@ -132,11 +142,18 @@ class NativeLifter:
             out = torch.empty((B, T_out, self.num_joints_out, 3), dtype=torch.float32,
                               device=self.device)
         with torch.cuda.device(self.device):
-            N.check(self._lib.vp3d_forward_windows(
+            N.check(self._lib.vp3d_forward_windows_pool(
                 self._h, seqs.kps.data_ptr(), seqs.f2, cams, seqs.seq_off.data_ptr(),
-                seqs.seq_len.data_ptr(), pairs.data_ptr(), B, int(window), int(lead), out.data_ptr(),
-                N.DTYPES[dtype], N.stream_ptr(self.device)), "vp3d_forward_windows")
+                seqs.seq_len.data_ptr(), int(seqs.n_seq), int(max(seqs.lengths)), pairs.data_ptr(), B,
+                int(window), int(lead), out.data_ptr(), N.DTYPES[dtype], N.stream_ptr(self.device)),
+                "vp3d_forward_windows")
         return out
+
+    def expand_table_mode(self) -> int:
+        """The path the last forward_windows took: 0 = the expand conv per window row, 1 = the
+        expand table read by block 1 through indirect rows, 2 = the table with the windows' rows
+        copied out (vp3d_expand_table_mode)."""
+        return self._lib.vp3d_expand_table_mode(self._h)
 
     # ---- f16x3 activation pre-scale ----
     def set_x3_prescale(self, p) -> None:

@@ -122,7 +122,8 @@ int vp3d_forward(vp3d_handle* h, const float* x, int B, int T, float* y, int dty
  * of small f16x3 batches) gave up waiting for its helper units -- its output was then
  * wrong -- or when an f16x3 forward split a value past the f16 range of its halves
  * (|x| > 65,504: checked where the input rows and every hidden activation are split) or
- * produced non-finite poses (run such inputs in fp32); the fault is cleared by this call.  (The next vp3d_forward* on the handle also
+ * produced non-finite poses (run such inputs in fp32), or when a pair of an expand-table
+ * forward (vp3d_forward_windows_pool) named a sequence outside the pool; the fault is cleared by this call.  (The next vp3d_forward* on the handle also
  * refuses with VP3D_ERR_STATE while the fault is pending, without synchronising -- every
  * dtype after a split-K timeout, f16x3 only after an f16x3 range fault.)  No
  * reference counterpart: torch raises asynchronous device errors at the next sync. */
@@ -146,6 +147,34 @@ int vp3d_sync_status(vp3d_handle* h, void* stream);
 int vp3d_forward_windows(vp3d_handle* h, const float* kps, int32_t f2, const float* cams,
                          const int64_t* seq_off, const int32_t* seq_len, const int32_t* pairs, int B,
                          int window, int lead, float* y, int dtype, void* stream);
+
+/* vp3d_forward_windows with the resident pool described: `n_seq` sequences (the entries of
+ * seq_off / seq_len that pairs may name), the longest of `max_len` frames.  The same poses, bit
+ * for bit.  Knowing the pool lets an f16x3 forward without the camera concat compute the expand
+ * conv (TemporalModel.py:126-127, :188-189) once per resident frame instead of once per window
+ * row -- its output depends on the sequence and the frame position alone -- into a table of
+ * n_seq * T_tab rows (T_tab = max_len + lead + twice the frames a window's rows step over, rounded
+ * up to 16: every window start, in or outside its sequence, maps to rows with its edge clamp)
+ * that block 1 reads through per-window row bases.  Taken, from the sizes alone, when the table
+ * has at most half the rows of the per-window expand output (n_seq * T_tab <= B * rows / 2), is
+ * smaller than 2 GiB and both block-1 convs run the tile kernels that read indirect rows
+ * (conv_gemm_a4: 1,024-channel shapes); otherwise the call is vp3d_forward_windows exactly.  Large evaluation
+ * batches over a resident set qualify; a training-size batch over a large set never does.
+ * VP3D_EXPAND_TABLE (read once per forward): 0 = never, 1 = whenever the table fits 2 GiB,
+ * copy = the table, then the windows' rows copied out of it for block 1 (also what block-1
+ * kernel forms without indirect rows get).  What differs from vp3d_forward_windows on this path:
+ *   - the f16x3 range guard (vp3d_sync_status) sees every frame of the n_seq sequences, not
+ *     only the frames some window uses: one non-finite resident frame faults the forward;
+ *   - a pair naming a sequence outside [0, n_seq) is a fault reported by vp3d_sync_status /
+ *     the next forward (window starts outside their sequence are edge-clamped as ever). */
+int vp3d_forward_windows_pool(vp3d_handle* h, const float* kps, int32_t f2, const float* cams,
+                              const int64_t* seq_off, const int32_t* seq_len, int32_t n_seq, int32_t max_len,
+                              const int32_t* pairs, int B, int window, int lead, float* y, int dtype,
+                              void* stream);
+/* The path the handle's last gathered forward took: 0 = the expand conv per window row, 1 = the
+ * expand table read by block 1 through indirect rows, 2 = the table with the windows' rows
+ * copied out.  -1 for a NULL handle.  (Diagnostics and tests.) */
+int vp3d_expand_table_mode(const vp3d_handle* h);
 
 /* ---- f16x3 activation pre-scale (opt-in; no reference counterpart) ----
  * The split-fp16 path stores every activation as hi = f16(a), lo = f16(a - hi); lo is an f16
