@@ -205,10 +205,24 @@ struct StreamBatchParams {
     int64_t out_stride;
     const int* t;             // [S] stream positions (read only: advanced by the trailing launch)
     const int* active;        // [S] nonzero = the slot takes part in this step
+    // Look-ahead form (a non-causal model seen `lookahead` frames late; all zero / null = the
+    // causal form above, whose instruction stream these fields do not touch).  `active` then
+    // holds step codes (kStreamCode*), t counts consume and drain steps and n the frames
+    // consumed; which slots take a step follows from (code, t, n) alone (stream_batch.hip).
+    const int* n;             // [S] frames consumed; non-null selects the look-ahead form
+    int lookahead;            // P = sum of the layers' pads: step t emits the pose of frame t - P
+    int res_back;             // the residual row is the block input of time max(t - res_back, 0)
+    int in_clamp;             // expand layer: raw-frame taps are clamped at the slot's last frame
+    int out_gate;             // shrink layer: a slot with t < out_gate stores no pose row
 };
+constexpr int kStreamCodeIdle = 0, kStreamCodeConsume = 1, kStreamCodeDrain = 2;
 hipError_t launch_stream_batch(const StreamBatchParams& q, Act wtype, hipStream_t s);
 // the step's last launch: t[s] += 1 for every active slot
 hipError_t launch_stream_batch_advance(int* t, const int* active, int S, hipStream_t s);
+// the look-ahead step's last launch: for every slot that takes the step t[s] += 1 (and n[s] += 1
+// if it consumes), pose_frame[s] = the frame whose pose row the step wrote, else -1
+hipError_t launch_stream_batch_advance_look(int* t, int* n, const int* codes, int* pose_frame, int lookahead, int S,
+                                            hipStream_t s);
 
 // Causal streaming, persistent form (stream_persist.hip): one launch runs `steps` frames;
 // workgroup g owns channels [g*CPW, (g+1)*CPW) of every layer with their 16-bit weights

@@ -16,6 +16,20 @@
 // are read once per 16-row tile instead of once per stream.  A slot with active[s] == 0 stores
 // nothing: no ring slot, no pose row; positions are advanced by a trailing launch.
 //
+// Look-ahead form (StreamBatchParams::n set): the same step for a NON-causal model
+// (TemporalModel.py:79-138 with causal=False, causal_shift = 0), seen P = sum of the layers'
+// pads frames late.  In arrival time every tap still reads t_s - (taps-1-k) dil clamped at 0;
+// what differs from the causal form:
+//   the residual is the centre tap of the block's k-conv window (TemporalModel.py:132 with
+//   causal_shift = 0): the block input of time max(t_s - pad_b, 0), not the newest row;
+//   a slot takes steps by code: 1 consumes its new frame, 2 drains -- a step whose newest frame
+//   is the slot's last consumed one, the right half of the reference's (pad, pad) edge padding
+//   (generators.py:193-198), got by clamping the expand's raw-frame taps at frame n_s - 1; the
+//   frame ring is not appended to;
+//   the shrink stores a pose row only once t_s >= P: the pose of frame t_s - P.
+// A slot's state is (t_s steps taken, n_s frames consumed): it has drained iff t_s > n_s and has
+// emitted max(t_s - P, 0) poses, so look_takes_step below needs no further counters.
+//
 // Arithmetic: the exact f32 MFMA (v_mfma_f32_16x16x4_f32) for every weight dtype.  Activations
 // stay f32; 16-bit weights are widened to f32 in registers, so only the weights are rounded
 // (the streams' contract, oracle/stream_ref.py).
@@ -77,12 +91,26 @@ struct W8<float> {
     __device__ __forceinline__ float get(int e) const { return e < 4 ? lo[e] : hi[e - 4]; }
 };
 
+// Look-ahead form: does a slot with step code `code`, t steps taken and n frames consumed take
+// this step?  Consume: only while the slot has never drained (t == n).  Drain: only with a
+// frame consumed and poses still owed (t - P < n).  Every layer's launch and the trailing
+// advance evaluate this on the same (code, t, n), so they agree.
+__device__ __forceinline__ bool look_takes_step(int code, int t, int n, int P) {
+    if (code == kStreamCodeConsume) return t == n;
+    if (code == kStreamCodeDrain) return n > 0 && t - P < n;
+    return false;
+}
+
 // VEC: cin and every per-slot stride are multiples of 4 floats, so a lane stages 4 consecutive
 // k (one tap) with one 16-byte load; otherwise one k per load (the expand: cin = J_in F)
-template <typename WT, bool VEC>
+//
+// LOOK: the look-ahead form (header comment).  A template flag, so that the causal form's
+// instruction stream stays what it was.
+template <typename WT, bool VEC, bool LOOK>
 __global__ __launch_bounds__(kThreads) void stream_batch_layer(StreamBatchParams q) {
     __shared__ __attribute__((aligned(16))) float x[kRows * kPitch];
     __shared__ int s_t[kRows], s_on[kRows];
+    __shared__ int s_hi[LOOK ? kRows : 1];  // LOOK: the newest raw frame the slot's expand may read
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 15, c = lane >> 4;
@@ -93,9 +121,20 @@ __global__ __launch_bounds__(kThreads) void stream_batch_layer(StreamBatchParams
 
     if (tid < kRows) {
         const int s = row0 + tid;
-        const bool on = s < q.S && q.active[s] != 0;
-        s_on[tid] = on ? 1 : 0;
-        s_t[tid] = on ? q.t[s] : 0;
+        if constexpr (LOOK) {
+            const int code = s < q.S ? q.active[s] : kStreamCodeIdle;
+            const int t = s < q.S ? q.t[s] : 0, n = s < q.S ? q.n[s] : 0;
+            const bool on = look_takes_step(code, t, n, q.lookahead);
+            s_on[tid] = on ? 1 : 0;
+            s_t[tid] = on ? t : 0;
+            // a consuming slot's newest frame is the new one (time t == n); a draining slot
+            // repeats frame n - 1, the reference's right edge padding
+            s_hi[tid] = on ? (code == kStreamCodeConsume ? t : n - 1) : 0;
+        } else {
+            const bool on = s < q.S && q.active[s] != 0;
+            s_on[tid] = on ? 1 : 0;
+            s_t[tid] = on ? q.t[s] : 0;
+        }
     }
 
     // the weights do not depend on the positions: the first chunk's loads go out before them
@@ -118,6 +157,9 @@ __global__ __launch_bounds__(kThreads) void stream_batch_layer(StreamBatchParams
         const int t = s_t[row];
         int tt = t - back;
         tt = tt < 0 ? 0 : tt;
+        if constexpr (LOOK) {
+            if (q.in_clamp) tt = tt > s_hi[row] ? s_hi[row] : tt;
+        }
         const int64_t s = row0 + row;
         if (q.in_frame && tt == t) return q.in_frame + s * q.cin;
         return q.in + s * q.in_stride + (q.in_R ? (int64_t)(tt & (q.in_R - 1)) * q.cin : 0);
@@ -128,6 +170,9 @@ __global__ __launch_bounds__(kThreads) void stream_batch_layer(StreamBatchParams
     if (q.in_ring_w && blockIdx.x == 0) {
         for (int row = wid; row < kRows; row += kWaves) {
             if (!s_on[row]) continue;
+            if constexpr (LOOK) {
+                if (s_hi[row] != s_t[row]) continue;  // a draining slot has no new frame
+            }
             const int64_t s = row0 + row;
             float* dst = q.in_ring_w + s * q.in_stride + (int64_t)(s_t[row] & (q.in_R - 1)) * q.cin;
             for (int ch = lane; ch < q.cin; ch += 64) dst[ch] = q.in_frame[s * q.cin + ch];
@@ -213,8 +258,15 @@ __global__ __launch_bounds__(kThreads) void stream_batch_layer(StreamBatchParams
             const int64_t slot = row0 + row;
             float y = s * q.scale[n] + q.shift[n];
             if (q.relu) y = y > 0.f ? y : 0.f;
-            if (q.res) y += q.res[slot * q.res_stride + (int64_t)(q.res_R ? (t & (q.res_R - 1)) : 0) * q.N + n];
-            q.out[slot * q.out_stride + (int64_t)(q.out_R ? (t & (q.out_R - 1)) : 0) * q.N + n] = y;
+            int tr = t;  // time of the residual row: the centre tap of the block's k-conv window
+            bool store = true;
+            if constexpr (LOOK) {
+                tr = t - q.res_back;
+                tr = tr < 0 ? 0 : tr;
+                store = t >= q.out_gate;
+            }
+            if (q.res) y += q.res[slot * q.res_stride + (int64_t)(q.res_R ? (tr & (q.res_R - 1)) : 0) * q.N + n];
+            if (store) q.out[slot * q.out_stride + (int64_t)(q.out_R ? (t & (q.out_R - 1)) : 0) * q.N + n] = y;
         }
     }
 }
@@ -224,12 +276,35 @@ __global__ __launch_bounds__(64) void stream_batch_advance(int* t, const int* ac
     if (s < S && active[s] != 0) t[s] += 1;
 }
 
-template <typename WT>
+__global__ __launch_bounds__(64) void stream_batch_advance_look(int* t, int* n, const int* codes, int* pose_frame,
+                                                               int P, int S) {
+    const int s = threadIdx.x;
+    if (s >= S) return;
+    const int code = codes[s], ts = t[s], ns = n[s];
+    const bool on = look_takes_step(code, ts, ns, P);
+    pose_frame[s] = on && ts >= P ? ts - P : -1;
+    if (on) {
+        t[s] = ts + 1;
+        if (code == kStreamCodeConsume) n[s] = ns + 1;
+    }
+}
+
+template <typename WT, bool LOOK>
 void launch_layer(const StreamBatchParams& q, bool vec, dim3 grid, hipStream_t s) {
     if (vec)
-        hipLaunchKernelGGL((stream_batch_layer<WT, true>), grid, dim3(kThreads), 0, s, q);
+        hipLaunchKernelGGL((stream_batch_layer<WT, true, LOOK>), grid, dim3(kThreads), 0, s, q);
     else
-        hipLaunchKernelGGL((stream_batch_layer<WT, false>), grid, dim3(kThreads), 0, s, q);
+        hipLaunchKernelGGL((stream_batch_layer<WT, false, LOOK>), grid, dim3(kThreads), 0, s, q);
+}
+
+template <bool LOOK>
+void launch_form(const StreamBatchParams& q, Act wtype, bool vec, dim3 grid, hipStream_t s) {
+    if (wtype == Act::F32)
+        launch_layer<float, LOOK>(q, vec, grid, s);
+    else if (wtype == Act::F16)
+        launch_layer<_Float16, LOOK>(q, vec, grid, s);
+    else
+        launch_layer<__bf16, LOOK>(q, vec, grid, s);
 }
 
 }  // namespace
@@ -242,18 +317,26 @@ hipError_t launch_stream_batch(const StreamBatchParams& q, Act wtype, hipStream_
     const bool vec = ((q.cin | (int)q.in_stride) & 3) == 0 && ((uintptr_t)q.in & 15) == 0 &&
                      ((uintptr_t)q.in_frame & 15) == 0;
     const dim3 grid((q.N + kCols - 1) / kCols, (q.S + kRows - 1) / kRows);
-    if (wtype == Act::F32)
-        launch_layer<float>(q, vec, grid, s);
-    else if (wtype == Act::F16)
-        launch_layer<_Float16>(q, vec, grid, s);
-    else
-        launch_layer<__bf16>(q, vec, grid, s);
+    if (q.n) {
+        if (q.lookahead < 0 || q.res_back < 0 || q.out_gate < 0) return hipErrorInvalidValue;
+        launch_form<true>(q, wtype, vec, grid, s);
+    } else {
+        if (q.lookahead || q.res_back || q.in_clamp || q.out_gate) return hipErrorInvalidValue;
+        launch_form<false>(q, wtype, vec, grid, s);
+    }
     return hipGetLastError();
 }
 
 hipError_t launch_stream_batch_advance(int* t, const int* active, int S, hipStream_t s) {
     if (S < 1 || S > kStreamBatchMax) return hipErrorInvalidValue;
     hipLaunchKernelGGL(stream_batch_advance, dim3(1), dim3(64), 0, s, t, active, S);
+    return hipGetLastError();
+}
+
+hipError_t launch_stream_batch_advance_look(int* t, int* n, const int* codes, int* pose_frame, int lookahead, int S,
+                                            hipStream_t s) {
+    if (S < 1 || S > kStreamBatchMax || lookahead < 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(stream_batch_advance_look, dim3(1), dim3(64), 0, s, t, n, codes, pose_frame, lookahead, S);
     return hipGetLastError();
 }
 

@@ -2073,17 +2073,32 @@ struct vp3d_mstream {
     std::vector<StreamBatchParams> steps;
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
+    // look-ahead form (vp3d_lstream): pos then also holds [S] frames consumed and [S] pose_frame,
+    // and the active words are step codes
+    bool look = false;
+    int lookahead = 0;
+};
+
+// a vp3d_mstream of the look-ahead form behind its own opaque type
+struct vp3d_lstream {
+    vp3d_mstream* m = nullptr;
 };
 
 namespace {
 
 int32_t* mstream_active(vp3d_mstream* m) { return (int32_t*)(m->pos + m->S); }
+int* mstream_consumed(vp3d_mstream* m) { return m->pos + 2 * m->S; }
+int32_t* mstream_pose_frame(vp3d_mstream* m) { return (int32_t*)(m->pos + 3 * m->S); }
 
 // one step on the io buffers: a launch per layer, then the positions
 int mstream_launch(vp3d_mstream* m, hipStream_t s) {
     const Act wt = m->dtype == VP3D_DTYPE_F32 ? Act::F32 : (m->dtype == VP3D_DTYPE_BF16 ? Act::BF16 : Act::F16);
     for (const StreamBatchParams& q : m->steps) HIP_TRY(launch_stream_batch(q, wt, s));
-    HIP_TRY(launch_stream_batch_advance(m->pos, mstream_active(m), m->S, s));
+    if (m->look)
+        HIP_TRY(launch_stream_batch_advance_look(m->pos, mstream_consumed(m), mstream_active(m), mstream_pose_frame(m),
+                                                 m->lookahead, m->S, s));
+    else
+        HIP_TRY(launch_stream_batch_advance(m->pos, mstream_active(m), m->S, s));
     return VP3D_OK;
 }
 
@@ -2098,19 +2113,22 @@ void mstream_free(vp3d_mstream* m) {
     delete m;
 }
 
-}  // namespace
-
-extern "C" {
-
-int vp3d_mstream_create(vp3d_handle* h, int dtype, int n_streams, vp3d_mstream** out) {
+// the buffers and per-layer launch parameters of a batched stream; look: the look-ahead form of
+// a non-causal model (vp3d_lstream), else the causal one (vp3d_mstream)
+int mstream_build(vp3d_handle* h, int dtype, int n_streams, bool look, vp3d_mstream** out) {
     if (!h || !out) return fail(VP3D_ERR_ARG, "NULL argument");
     *out = nullptr;
     if (dtype < 0 || dtype > 2) return fail(VP3D_ERR_ARG, "unknown dtype");
     if (n_streams < 1 || n_streams > VP3D_MSTREAM_MAX)
         return fail(VP3D_ERR_ARG, "n_streams must be 1.." + std::to_string(VP3D_MSTREAM_MAX));
     static_assert(VP3D_MSTREAM_MAX == kStreamBatchMax, "the kernel's slot limit is the ABI's");
-    if (h->cfg.variant != VP3D_VARIANT_DILATED || !h->cfg.causal)
+    if (look) {
+        if (h->cfg.variant != VP3D_VARIANT_DILATED)
+            return fail(VP3D_ERR_ARG, "look-ahead streaming needs a dilated TemporalModel (not the strided variant)");
+        if (h->cfg.causal) return fail(VP3D_ERR_ARG, "causal TemporalModel, look-ahead 0: use vp3d_mstream");
+    } else if (h->cfg.variant != VP3D_VARIANT_DILATED || !h->cfg.causal) {
         return fail(VP3D_ERR_ARG, "streaming needs a causal dilated TemporalModel");
+    }
     for (const Layer& L : h->layers)
         if (L.Kp > 4096) return fail(VP3D_ERR_ARG, "streaming supports K <= 4096 per layer");
     int dev = 0;
@@ -2121,6 +2139,9 @@ int vp3d_mstream_create(vp3d_handle* h, int dtype, int n_streams, vp3d_mstream**
     m->h = h;
     m->dtype = dtype;
     m->S = n_streams;
+    m->look = look;
+    for (int p : h->pad) m->lookahead += look ? p : 0;
+    const size_t pos_bytes = (look ? 16 : 8) * (size_t)n_streams;
     const int S = n_streams;
     const int C = h->cfg.channels;
     const int nl = (int)h->layers.size();
@@ -2138,14 +2159,15 @@ int vp3d_mstream_create(vp3d_handle* h, int dtype, int n_streams, vp3d_mstream**
     };
     add_ring(h->layers[0], cin0);
     for (int b = 1; b <= nb; ++b) add_ring(h->layers[2 * b - 1], C);
-    if (hipMalloc(&m->pos, 8 * (size_t)S) != hipSuccess || hipMalloc(&m->frames, 4 * (size_t)S * cin0) != hipSuccess ||
+    if (hipMalloc(&m->pos, pos_bytes) != hipSuccess || hipMalloc(&m->frames, 4 * (size_t)S * cin0) != hipSuccess ||
         hipMalloc(&m->poses, 4 * (size_t)S * nout) != hipSuccess ||
         hipMalloc(&m->rings, 4 * (size_t)S * ring_floats) != hipSuccess ||
         hipMalloc(&m->scratch, 8 * (size_t)S * C) != hipSuccess) {
         mstream_free(m);
         return fail(VP3D_ERR_OOM, "batched stream buffers");
     }
-    hipMemset(m->pos, 0, 8 * (size_t)S);
+    hipMemset(m->pos, 0, pos_bytes);
+    if (look) hipMemset(mstream_pose_frame(m), 0xff, 4 * (size_t)S);  // -1: no pose row written yet
     hipMemset(m->frames, 0, 4 * (size_t)S * cin0);
     hipMemset(m->poses, 0, 4 * (size_t)S * nout);
     hipMemset(m->rings, 0, 4 * (size_t)S * ring_floats);
@@ -2167,6 +2189,10 @@ int vp3d_mstream_create(vp3d_handle* h, int dtype, int n_streams, vp3d_mstream**
         q.S = S;
         q.t = m->pos;
         q.active = mstream_active(m);
+        if (look) {
+            q.n = mstream_consumed(m);
+            q.lookahead = m->lookahead;
+        }
         return q;
     };
     auto ring_in = [&](StreamBatchParams& q, int i) {
@@ -2194,6 +2220,7 @@ int vp3d_mstream_create(vp3d_handle* h, int dtype, int n_streams, vp3d_mstream**
         ring_in(q, 0);
         q.in_frame = m->frames;
         q.in_ring_w = m->rings + ring_off[0];
+        q.in_clamp = look ? 1 : 0;
         out_to(q, 1);
         m->steps.push_back(q);
     }
@@ -2208,6 +2235,9 @@ int vp3d_mstream_create(vp3d_handle* h, int dtype, int n_streams, vp3d_mstream**
         pw.res = m->rings + ring_off[b];
         pw.res_R = ring_len[b];
         pw.res_stride = (int64_t)ring_floats;
+        // non-causal: the centre tap of the k-conv window (TemporalModel.py:132, causal_shift = 0);
+        // ring b holds (taps - 1) dil + 1 >= 2 pad_b + 1 slots
+        pw.res_back = look ? h->pad[b] : 0;
         out_to(pw, b + 1);
         m->steps.push_back(pw);
     }
@@ -2216,11 +2246,42 @@ int vp3d_mstream_create(vp3d_handle* h, int dtype, int n_streams, vp3d_mstream**
         plain_in(q, xlast);
         q.out = m->poses;
         q.out_stride = nout;
+        q.out_gate = m->lookahead;
         m->steps.push_back(q);
     }
     hipDeviceSynchronize();  // setup memsets (legacy stream) before any launch on another stream
     *out = m;
     return VP3D_OK;
+}
+
+int mstream_capture(vp3d_mstream* m, void* stream) {
+    if (!stream) return fail(VP3D_ERR_ARG, "graph capture needs a non-default stream");
+    hipStream_t s = (hipStream_t)stream;
+    if (m->exec) {
+        hipGraphExecDestroy(m->exec);
+        m->exec = nullptr;
+    }
+    if (m->graph) {
+        hipGraphDestroy(m->graph);
+        m->graph = nullptr;
+    }
+    HIP_TRY(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+    int rc = mstream_launch(m, s);
+    hipGraph_t g = nullptr;
+    hipError_t e = hipStreamEndCapture(s, &g);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(VP3D_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
+    m->graph = g;
+    HIP_TRY(hipGraphInstantiate(&m->exec, g, nullptr, nullptr, 0));
+    return VP3D_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vp3d_mstream_create(vp3d_handle* h, int dtype, int n_streams, vp3d_mstream** out) {
+    return mstream_build(h, dtype, n_streams, false, out);
 }
 
 int vp3d_mstream_io(vp3d_mstream* m, float** frames, int32_t** active, float** poses) {
@@ -2267,25 +2328,7 @@ int vp3d_mstream_frames_seen(vp3d_mstream* m, int64_t* out) {
 
 int vp3d_mstream_graph_capture(vp3d_mstream* m, void* stream) {
     if (!m) return fail(VP3D_ERR_ARG, "mstream is NULL");
-    if (!stream) return fail(VP3D_ERR_ARG, "graph capture needs a non-default stream");
-    hipStream_t s = (hipStream_t)stream;
-    if (m->exec) {
-        hipGraphExecDestroy(m->exec);
-        m->exec = nullptr;
-    }
-    if (m->graph) {
-        hipGraphDestroy(m->graph);
-        m->graph = nullptr;
-    }
-    HIP_TRY(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    int rc = mstream_launch(m, s);
-    hipGraph_t g = nullptr;
-    hipError_t e = hipStreamEndCapture(s, &g);
-    if (rc) return rc;
-    if (e != hipSuccess) return fail(VP3D_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
-    m->graph = g;
-    HIP_TRY(hipGraphInstantiate(&m->exec, g, nullptr, nullptr, 0));
-    return VP3D_OK;
+    return mstream_capture(m, stream);
 }
 
 int vp3d_mstream_graph_launch(vp3d_mstream* m, void* stream) {
@@ -2297,6 +2340,97 @@ int vp3d_mstream_graph_launch(vp3d_mstream* m, void* stream) {
 int vp3d_mstream_destroy(vp3d_mstream* m) {
     if (!m) return VP3D_OK;
     mstream_free(m);
+    return VP3D_OK;
+}
+
+// ---- look-ahead streaming of non-causal models (stream_batch.hip, look-ahead form) ----
+
+int vp3d_lstream_create(vp3d_handle* h, int dtype, int n_streams, vp3d_lstream** out) {
+    if (!h || !out) return fail(VP3D_ERR_ARG, "NULL argument");
+    *out = nullptr;
+    vp3d_mstream* m = nullptr;
+    int rc = mstream_build(h, dtype, n_streams, true, &m);
+    if (rc) return rc;
+    vp3d_lstream* l = new vp3d_lstream();
+    l->m = m;
+    *out = l;
+    return VP3D_OK;
+}
+
+int vp3d_lstream_lookahead(vp3d_lstream* l, int32_t* out) {
+    if (!l || !out) return fail(VP3D_ERR_ARG, "NULL argument");
+    *out = l->m->lookahead;
+    return VP3D_OK;
+}
+
+int vp3d_lstream_io(vp3d_lstream* l, float** frames, int32_t** codes, float** poses, int32_t** pose_frame) {
+    if (!l) return fail(VP3D_ERR_ARG, "lstream is NULL");
+    if (frames) *frames = l->m->frames;
+    if (codes) *codes = mstream_active(l->m);
+    if (poses) *poses = l->m->poses;
+    if (pose_frame) *pose_frame = mstream_pose_frame(l->m);
+    return VP3D_OK;
+}
+
+int vp3d_lstream_step(vp3d_lstream* l, const float* frames, const int32_t* codes, float* poses, int32_t* pose_frame,
+                      void* stream) {
+    if (!l) return fail(VP3D_ERR_ARG, "lstream is NULL");
+    vp3d_mstream* m = l->m;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t cin0 = m->h->layers[0].cin, nout = m->h->layers.back().cout;
+    if (frames) HIP_TRY(hipMemcpyAsync(m->frames, frames, 4 * m->S * cin0, hipMemcpyDeviceToDevice, s));
+    if (codes)
+        HIP_TRY(hipMemcpyAsync(mstream_active(m), codes, 4 * (size_t)m->S, hipMemcpyDeviceToDevice, s));
+    else if (frames)
+        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)mstream_active(m), kStreamCodeConsume, (size_t)m->S, s));
+    int rc = mstream_launch(m, s);
+    if (rc) return rc;
+    if (poses) HIP_TRY(hipMemcpyAsync(poses, m->poses, 4 * m->S * nout, hipMemcpyDeviceToDevice, s));
+    if (pose_frame)
+        HIP_TRY(hipMemcpyAsync(pose_frame, mstream_pose_frame(m), 4 * (size_t)m->S, hipMemcpyDeviceToDevice, s));
+    return VP3D_OK;
+}
+
+int vp3d_lstream_reset(vp3d_lstream* l, int slot, void* stream) {
+    if (!l) return fail(VP3D_ERR_ARG, "lstream is NULL");
+    vp3d_mstream* m = l->m;
+    if (slot < -1 || slot >= m->S) return fail(VP3D_ERR_ARG, "slot must be -1 or 0..n_streams-1");
+    // steps taken and frames consumed; the poses emitted and the drained state follow from them
+    const size_t first = slot < 0 ? 0 : (size_t)slot, bytes = slot < 0 ? 4 * (size_t)m->S : 4;
+    HIP_TRY(hipMemsetAsync(m->pos + first, 0, bytes, (hipStream_t)stream));
+    HIP_TRY(hipMemsetAsync(mstream_consumed(m) + first, 0, bytes, (hipStream_t)stream));
+    return VP3D_OK;
+}
+
+int vp3d_lstream_counts(vp3d_lstream* l, int64_t* consumed, int64_t* emitted) {
+    if (!l || (!consumed && !emitted)) return fail(VP3D_ERR_ARG, "NULL argument");
+    vp3d_mstream* m = l->m;
+    std::vector<int> tn(3 * (size_t)m->S);  // t, codes (unused), n
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(tn.data(), m->pos, 12 * (size_t)m->S, hipMemcpyDeviceToHost));
+    for (int s = 0; s < m->S; ++s) {
+        const int t = tn[s], n = tn[2 * (size_t)m->S + s];
+        if (consumed) consumed[s] = n;
+        if (emitted) emitted[s] = t > m->lookahead ? t - m->lookahead : 0;
+    }
+    return VP3D_OK;
+}
+
+int vp3d_lstream_graph_capture(vp3d_lstream* l, void* stream) {
+    if (!l) return fail(VP3D_ERR_ARG, "lstream is NULL");
+    return mstream_capture(l->m, stream);
+}
+
+int vp3d_lstream_graph_launch(vp3d_lstream* l, void* stream) {
+    if (!l || !l->m->exec) return fail(VP3D_ERR_STATE, "no captured graph");
+    HIP_TRY(hipGraphLaunch(l->m->exec, (hipStream_t)stream));
+    return VP3D_OK;
+}
+
+int vp3d_lstream_destroy(vp3d_lstream* l) {
+    if (!l) return VP3D_OK;
+    mstream_free(l->m);
+    delete l;
     return VP3D_OK;
 }
 

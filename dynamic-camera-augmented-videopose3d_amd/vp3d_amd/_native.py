@@ -59,6 +59,9 @@ EXPORTS = [
     "vp3d_mstream_create", "vp3d_mstream_io", "vp3d_mstream_step", "vp3d_mstream_reset",
     "vp3d_mstream_frames_seen", "vp3d_mstream_graph_capture", "vp3d_mstream_graph_launch",
     "vp3d_mstream_destroy",
+    "vp3d_lstream_create", "vp3d_lstream_lookahead", "vp3d_lstream_io", "vp3d_lstream_step",
+    "vp3d_lstream_reset", "vp3d_lstream_counts", "vp3d_lstream_graph_capture", "vp3d_lstream_graph_launch",
+    "vp3d_lstream_destroy",
     "vp3d_trainer_create", "vp3d_trainer_destroy", "vp3d_train_forward", "vp3d_train_backward",
     "vp3d_train_dropout_mask", "vp3d_train_relu_mask", "vp3d_train_layer_rows", "vp3d_train_reduce_doubles", "vp3d_adam_step", "vp3d_mpjpe_backward",
     "vp3d_seq_weight_count", "vp3d_seq_create", "vp3d_seq_destroy", "vp3d_seq_forward",
@@ -197,6 +200,16 @@ _SIGNATURES = {
     "vp3d_mstream_graph_capture": (_int, [_vp, _vp]),
     "vp3d_mstream_graph_launch": (_int, [_vp, _vp]),
     "vp3d_mstream_destroy": (_int, [_vp]),
+    "vp3d_lstream_create": (_int, [_vp, _int, _int, ctypes.POINTER(_vp)]),
+    "vp3d_lstream_lookahead": (_int, [_vp, ctypes.POINTER(ctypes.c_int32)]),
+    "vp3d_lstream_io": (_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp),
+                               ctypes.POINTER(_vp)]),
+    "vp3d_lstream_step": (_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "vp3d_lstream_reset": (_int, [_vp, _int, _vp]),
+    "vp3d_lstream_counts": (_int, [_vp, _vp, _vp]),
+    "vp3d_lstream_graph_capture": (_int, [_vp, _vp]),
+    "vp3d_lstream_graph_launch": (_int, [_vp, _vp]),
+    "vp3d_lstream_destroy": (_int, [_vp]),
     "vp3d_trainer_create": (_int, [ctypes.POINTER(vp3d_cfg), ctypes.POINTER(_vp)]),
     "vp3d_trainer_destroy": (_int, [_vp]),
     "vp3d_train_forward": (_int, [_vp, ctypes.POINTER(_vp), _int, _vp, _int, _int, ctypes.c_float,

@@ -12,6 +12,11 @@ sequence (UnchunkedGenerator, generators.py:193-198, causal_shift = pad).
 
 CausalStreamBatch advances many such streams in one step (vp3d_mstream,
 csrc/stream_batch.hip): one skinny-GEMM launch per layer over all of them.
+
+LookaheadStreamBatch runs the same batched step for a NON-causal TemporalModel (causal=False,
+the reference's default), (receptive field - 1) / 2 frames late, with a drain at the end of a
+sequence for the reference's right edge padding (vp3d_lstream); lift_sequences schedules whole
+ragged sequences over its slots.
 """
 from __future__ import annotations
 
@@ -285,6 +290,184 @@ class CausalStreamBatch:
             self.close()
         except Exception:
             pass
+
+
+class LookaheadStreamBatch:
+    """`n_streams` slots of one NON-causal lifter (the reference's default, TemporalModel.py:79-138
+    with causal=False) advanced together, each `lookahead` = (receptive field - 1) / 2 frames late.
+
+    Wraps vp3d_lstream (include/vp3d.h; the look-ahead form of csrc/stream_batch.hip).  Per step a
+    slot gets a code: IDLE, CONSUME (its frame) or DRAIN (a step that repeats its last consumed
+    frame, the reference's right edge padding, generators.py:193-198).  A step taken with
+    `lookahead` or more steps behind it writes the pose of frame t - lookahead into the slot's
+    row and reports that frame index in pose_frame (-1: no row written).  After n frames and
+    `lookahead` drains a slot has emitted n poses, pose k being frame k of the reference's
+    whole-sequence evaluation of those n frames; reset the slot for the next sequence.
+    """
+
+    IDLE, CONSUME, DRAIN = 0, 1, 2
+
+    def __init__(self, lifter, n_streams: int, dtype: str = "fp16"):
+        """lifter: a NativeLifter (``model.native_lifter()``) of a non-causal TemporalModel."""
+        self._lib = N.load()
+        self.lifter = lifter
+        self.device = lifter.device
+        self.dtype = dtype
+        self.n_streams = int(n_streams)
+        self._l = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            rc = self._lib.vp3d_lstream_create(lifter._h, N.DTYPES[dtype], self.n_streams, ctypes.byref(self._l))
+            if rc and lifter.cfg.causal:
+                raise RuntimeError("vp3d: vp3d_lstream_create: " + self._lib.vp3d_last_error().decode()
+                                   + " (CausalStreamBatch)")
+            N.check(rc, "vp3d_lstream_create")
+        la = ctypes.c_int32()
+        N.check(self._lib.vp3d_lstream_lookahead(self._l, ctypes.byref(la)), "vp3d_lstream_lookahead")
+        self.lookahead = int(la.value)
+        f, c, p, k = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+        N.check(self._lib.vp3d_lstream_io(self._l, ctypes.byref(f), ctypes.byref(c), ctypes.byref(p), ctypes.byref(k)))
+        self._io_ptrs = (f.value, c.value, p.value, k.value)
+        self.j_in, self.in_features = lifter.cfg.num_joints_in, lifter.cfg.in_features
+        self.n_in = self.j_in * self.in_features
+        self.n_out = lifter.cfg.num_joints_out * 3
+        self._graph_stream = None
+
+    def step(self, frames: torch.Tensor, codes: torch.Tensor | None = None, out: torch.Tensor | None = None):
+        """frames: (S, J_in, F) float32 on the device; codes: (S,) device tensor of an integer or
+        bool dtype (0 idle, 1 consume, 2 drain), None = every slot consumes
+        -> (poses (S, J_out, 3) float32, pose_frame (S,) int32): row s holds the pose of frame
+        pose_frame[s] of slot s's sequence if this step wrote it (pose_frame[s] >= 0), else what
+        it held before (zeros before the slot's first pose)."""
+        S = self.n_streams
+        if not frames.is_cuda or (codes is not None and not codes.is_cuda):
+            raise RuntimeError("vp3d: stream frames must be HIP device tensors (no CPU fallback)")
+        if tuple(frames.shape) != (S, self.j_in, self.in_features):
+            raise RuntimeError(f"vp3d: frames must be ({S}, {self.j_in}, {self.in_features}), got {tuple(frames.shape)}")
+        frames = frames.contiguous().float()
+        c_ptr = None
+        if codes is not None:
+            if tuple(codes.shape) != (S,) or codes.dtype.is_floating_point or codes.dtype.is_complex:
+                raise RuntimeError(f"vp3d: codes must be an integer or bool tensor of shape ({S},)")
+            codes = codes.to(torch.int32).contiguous()
+            c_ptr = codes.data_ptr()
+        if out is None:
+            out = torch.empty((S, self.n_out // 3, 3), dtype=torch.float32, device=self.device)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.numel() == S * self.n_out
+        pose_frame = torch.empty(S, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            N.check(self._lib.vp3d_lstream_step(self._l, frames.data_ptr(), c_ptr, out.data_ptr(),
+                                                pose_frame.data_ptr(), N.stream_ptr(self.device)), "vp3d_lstream_step")
+        return out, pose_frame
+
+    def reset(self, slot: int | None = None) -> None:
+        """Restart one slot (None: every slot): its next frame is frame 0 of a new sequence."""
+        with torch.cuda.device(self.device):
+            N.check(self._lib.vp3d_lstream_reset(self._l, -1 if slot is None else int(slot),
+                                                 N.stream_ptr(self.device)), "vp3d_lstream_reset")
+
+    def counts(self):
+        """(frames consumed, poses emitted) per slot: two (S,) int64 arrays (synchronises)."""
+        n = np.zeros(self.n_streams, dtype=np.int64)
+        e = np.zeros(self.n_streams, dtype=np.int64)
+        with torch.cuda.device(self.device):
+            N.check(self._lib.vp3d_lstream_counts(self._l, n.ctypes.data, e.ctypes.data), "vp3d_lstream_counts")
+        return n, e
+
+    # ---- hipGraph replay: one step reading / writing the io buffers ----
+    def io_tensors(self):
+        """(frames (S, J_in*F) float32, codes (S,) int32, poses (S, J_out*3) float32, pose_frame
+        (S,) int32) views of the device buffers a replayed step reads and writes."""
+        S = self.n_streams
+        f, c, p, k = self._io_ptrs
+        return (_wrap(f, S * self.n_in, self.device).view(S, self.n_in),
+                _wrap(c, S, self.device, "<i4"),
+                _wrap(p, S * self.n_out, self.device).view(S, self.n_out),
+                _wrap(k, S, self.device, "<i4"))
+
+    def capture(self, stream: torch.cuda.Stream) -> None:
+        """Capture one step into a hipGraph on `stream` (not the default stream)."""
+        self._graph_stream = stream
+        with torch.cuda.device(self.device):
+            N.check(self._lib.vp3d_lstream_graph_capture(self._l, stream.cuda_stream), "vp3d_lstream_graph_capture")
+
+    def replay(self, stream: torch.cuda.Stream | None = None) -> None:
+        s = stream if stream is not None else self._graph_stream
+        N.check(self._lib.vp3d_lstream_graph_launch(self._l, s.cuda_stream), "vp3d_lstream_graph_launch")
+
+    def lift_sequences(self, seqs):
+        """Lift any number of ragged sequences, each a (T_i, J_in, F) device tensor, over the
+        slots: a free slot takes the next sequence, consumes it a frame per step, drains
+        `lookahead` steps and is reset for the one after.  Returns a list of (T_i, J_out, 3)
+        float32 device tensors, each exactly what stepping that sequence by hand gives.
+
+        Costs one small host-to-device upload (the step codes) per step.  Which frame a pose
+        row belongs to is mirrored on the host instead of read back from pose_frame: the
+        mirror holds because this method resets every slot on entry and each slot again
+        before it takes a new sequence, so no state a caller left in the batch can reach it
+        (and whatever the slots held before the call is discarded)."""
+        S, P = self.n_streams, self.lookahead
+        seqs = list(seqs)
+        for x in seqs:
+            if not x.is_cuda:
+                raise RuntimeError("vp3d: stream frames must be HIP device tensors (no CPU fallback)")
+            if x.dim() != 3 or tuple(x.shape[1:]) != (self.j_in, self.in_features):
+                raise RuntimeError(f"vp3d: a sequence must be (T, {self.j_in}, {self.in_features}), got {tuple(x.shape)}")
+        seqs = [x.contiguous().float() for x in seqs]
+        outs = [torch.empty((x.shape[0], self.n_out // 3, 3), dtype=torch.float32, device=self.device) for x in seqs]
+        self.reset()
+        nxt = 0
+        cur = [-1] * S   # the sequence a slot carries, -1 = free
+        took = [0] * S   # steps the slot has taken on it
+        frames = torch.zeros((S, self.j_in, self.in_features), dtype=torch.float32, device=self.device)
+        poses = torch.empty((S, self.n_out // 3, 3), dtype=torch.float32, device=self.device)
+        while True:
+            codes = [self.IDLE] * S
+            for s in range(S):
+                if cur[s] < 0:
+                    while nxt < len(seqs) and seqs[nxt].shape[0] == 0:
+                        nxt += 1
+                    if nxt == len(seqs):
+                        continue
+                    cur[s], took[s], nxt = nxt, 0, nxt + 1
+                    self.reset(s)
+                x = seqs[cur[s]]
+                if took[s] < x.shape[0]:
+                    codes[s] = self.CONSUME
+                    frames[s].copy_(x[took[s]])
+                else:
+                    codes[s] = self.DRAIN
+            if not any(codes):
+                break
+            self.step(frames, torch.tensor(codes, dtype=torch.int32).to(self.device, non_blocking=True), out=poses)
+            for s in range(S):
+                if codes[s] == self.IDLE:
+                    continue
+                if took[s] >= P:  # this step wrote the pose of frame took - P (the host mirrors pose_frame)
+                    outs[cur[s]][took[s] - P].copy_(poses[s])
+                took[s] += 1
+                if took[s] == seqs[cur[s]].shape[0] + P:
+                    cur[s] = -1
+        return outs
+
+    def close(self) -> None:
+        if self._l:
+            self._lib.vp3d_lstream_destroy(self._l)
+            self._l = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def lift_sequences(lifter, seqs, n_streams: int = 16, dtype: str = "fp16"):
+    """LookaheadStreamBatch(lifter, n_streams, dtype).lift_sequences(seqs) on a batch of its own."""
+    bt = LookaheadStreamBatch(lifter, n_streams, dtype)
+    try:
+        return bt.lift_sequences(seqs)
+    finally:
+        bt.close()
 
 
 class _DevBuf:

@@ -352,6 +352,66 @@ int vp3d_mstream_graph_capture(vp3d_mstream* m, void* stream);
 int vp3d_mstream_graph_launch(vp3d_mstream* m, void* stream);
 int vp3d_mstream_destroy(vp3d_mstream* m);
 
+/* ---- look-ahead streaming: non-causal models on live tracks, batched, with drain ----
+ * The batched step above for a NON-causal TemporalModel (TemporalModel.py:79-138 with
+ * causal=False, the reference's default and what its 243-frame checkpoints are).  A non-causal
+ * dilated stack is the causal stack seen lookahead = (receptive field - 1) / 2 frames late: in
+ * arrival time every layer still reads taps at t - (taps-1-k) * dilation, clamped at the stream
+ * start; a block's residual is the centre tap of its k-conv window (TemporalModel.py:132 with
+ * causal_shift = 0), the block input pad_b steps back; and the end of a sequence is edge-padded
+ * on the right as well (UnchunkedGenerator, generators.py:193-198: (pad, pad) copies), which a
+ * slot gets by draining.  Pose k of a slot equals frame k of the reference's whole-sequence
+ * evaluation (run.py:689-724, evaluate() on one UnchunkedGenerator sequence) of the n frames
+ * the slot consumed.
+ *
+ * Per step every slot gets a code: 0 idle, 1 consume its frame, 2 drain (a step whose new frame
+ * repeats the slot's last consumed one); any other value is idle.  A slot counts n, the frames
+ * consumed, and t, the steps taken (consume + drain).  A step with t >= lookahead writes the pose
+ * of frame t - lookahead into the slot's pose row; earlier steps run every layer (the rings
+ * fill) but write no row, and a row that is not written keeps its content (zeros at first).
+ * After n frames and `lookahead` drains a slot has emitted exactly n poses.  No-ops -- nothing
+ * stored, no counter changed, pose_frame -1: a drain with n == 0 or with n poses emitted, and a
+ * consume once the slot has drained (until it is reset). */
+typedef struct vp3d_lstream vp3d_lstream;
+
+/* Accepts a non-causal dilated or dense TemporalModel (TemporalModel.py:79-138), K <= 4096 per
+ * layer, dtype F32 / F16 / BF16, 1 <= n_streams <= VP3D_MSTREAM_MAX; VP3D_ERR_ARG with a message
+ * otherwise (a causal model: "look-ahead 0: use vp3d_mstream"; the strided
+ * TemporalModelOptimized1f, :141-198; other dtypes).  Shares the handle's device weights. */
+int vp3d_lstream_create(vp3d_handle* h, int dtype, int n_streams, vp3d_lstream** out);
+/* The look-ahead in frames: the sum of the layers' pads (TemporalModel.py:31,107-111), 121 at
+ * receptive field 243. */
+int vp3d_lstream_lookahead(vp3d_lstream* l, int32_t* out);
+/* The device io buffers a step reads / writes: frames (S, J_in * F) f32, codes (S) int32,
+ * poses (S, J_out * 3) f32, pose_frame (S) int32 -- the frame index of the pose row the last
+ * step wrote for the slot, or -1 (generators.py:193-198: frame k of the padded sequence's
+ * output). */
+int vp3d_lstream_io(vp3d_lstream* l, float** frames, int32_t** codes, float** poses, int32_t** pose_frame);
+/* One step (the reference's model(inputs_2d), run.py:689-724, one frame at a time and
+ * `lookahead` frames late).  frames / codes / poses / pose_frame: device pointers copied into /
+ * out of the io buffers asynchronously, or NULL to use the io buffers as they are; codes == NULL
+ * with frames != NULL means every slot consumes. */
+int vp3d_lstream_step(vp3d_lstream* l, const float* frames, const int32_t* codes, float* poses, int32_t* pose_frame,
+                      void* stream);
+/* Restart slot `slot` (-1 = every slot) for a new sequence through the reference's generator
+ * (generators.py:193-198): frames consumed, steps taken, poses emitted and the drained state go
+ * to 0.  Async on `stream`; rings and pose rows are not cleared. */
+int vp3d_lstream_reset(vp3d_lstream* l, int slot, void* stream);
+/* Frames consumed and poses emitted so far by each slot (host arrays of n_streams entries,
+ * either may be NULL; synchronises with the device).  A sequence of the reference's generator
+ * (generators.py:193-198) is done when emitted == consumed. */
+int vp3d_lstream_counts(vp3d_lstream* l, int64_t* consumed, int64_t* emitted);
+/* Capture one step (reading / writing the io buffers, pose_frame included; run.py:689-724 per
+ * frame) into a hipGraph on `stream` (not the legacy default stream); replay with
+ * vp3d_lstream_graph_launch. */
+int vp3d_lstream_graph_capture(vp3d_lstream* l, void* stream);
+/* Replay the captured step on `stream`: one model(inputs_2d) per slot (run.py:689-724) on the
+ * frames and codes in the io buffers; VP3D_ERR_STATE without a captured graph. */
+int vp3d_lstream_graph_launch(vp3d_lstream* l, void* stream);
+/* Free the slots' rings, io buffers and graph; the handle and its weights (the TemporalModel's,
+ * TemporalModel.py:79-138) stay.  NULL is VP3D_OK. */
+int vp3d_lstream_destroy(vp3d_lstream* l);
+
 /* ---- training step (run.py:451-487, :662) ----
  * The reference trains TemporalModel in train mode: BatchNorm1d on batch
  * statistics with a running-stat update (TemporalModel.py:117,119; momentum
