@@ -1262,12 +1262,18 @@ static int a4_hn_tail(const ConvGemmParams& p, int ntiles, bool x3, int* level =
 static bool a4_tail_split(const ConvGemmParams& p, int mt_tail, int level, bool need_ws);
 static bool a4_indirect(const ConvGemmParams& p);
 
-bool conv_gemm_a4_x3_eligible(const ConvGemmParams& p, bool out_f32) {
+// the shapes and alignments the f16x3 tiles take, whatever the tile count
+static bool a4_x3_shape_ok(const ConvGemmParams& p, bool out_f32) {
     if (p.Ktap % GK != 0 || p.Kp % GK != 0 || p.lda % 8 != 0) return false;
     if (p.N % GN != 0 || p.N > GMAXN || p.ldy % (out_f32 ? 4 : 8) != 0 || (p.R && p.ldr % 8 != 0)) return false;
     if ((reinterpret_cast<uintptr_t>(p.A) & 15) || (reinterpret_cast<uintptr_t>(p.Y) & 15) ||
         (reinterpret_cast<uintptr_t>(p.W) & 15) || (p.R && (reinterpret_cast<uintptr_t>(p.R) & 15)))
         return false;
+    return (size_t)p.N * p.Kp < (1u << 31);
+}
+
+bool conv_gemm_a4_x3_eligible(const ConvGemmParams& p, bool out_f32) {
+    if (!a4_x3_shape_ok(p, out_f32)) return false;
     // enough tiles to fill the CUs (as the 16-bit dispatch: >= 384 tiles of 256 x 256), or a
     // half-N or split plan that does
     const int ntiles = ((p.M + GM - 1) / GM) * (p.N / GN);
@@ -1384,9 +1390,11 @@ static bool a4_indirect(const ConvGemmParams& p) { return p.T_in < 0 || (p.R != 
 
 // an f16x3 layer with indirect windows (T_in < 0 / R_T < 0, gemm::window_rows) runs on a4 when its
 // launch is whole tiles with a half-N / quarter-N tail at most: the split-K plans and the
-// split-K tail (conv_gemm_tail.hip) address their rows themselves
-bool conv_gemm_a4_x3_indirect_ok(const ConvGemmParams& p) {
-    if (!conv_gemm_a4_x3_eligible(p, false)) return false;
+// split-K tail (conv_gemm_tail.hip) address their rows themselves.  `any_fill`: also below the
+// tile count from which a4 is the layer's kernel otherwise (a partial round of whole tiles: the
+// first per-window block over a frame table, whose rows no other kernel can read)
+bool conv_gemm_a4_x3_indirect_ok(const ConvGemmParams& p, bool any_fill) {
+    if (!(any_fill ? a4_x3_shape_ok(p, false) : conv_gemm_a4_x3_eligible(p, false))) return false;
     const int ntiles = ((p.M + GM - 1) / GM) * (p.N / GN);
     const char* we = getenv("VP3D_A4_WALK");
     int level = 1;
@@ -1470,7 +1478,7 @@ hipError_t launch_conv_gemm_a4_x3(const ConvGemmParams& p_in, bool out_f32, hipS
     // indirect windows (gemm::window_rows; the caller asked conv_gemm_a4_x3_indirect_ok): the
     // whole, half-N and quarter-N tiles of the split rows form only
     const bool ix = a4_indirect(p);
-    if (ix && (out_f32 || !conv_gemm_a4_x3_indirect_ok(p))) return hipErrorInvalidValue;
+    if (ix && (out_f32 || !conv_gemm_a4_x3_indirect_ok(p, true))) return hipErrorInvalidValue;
 #ifndef VP3D_ABLATION
     if (hn_tail > 0) {
         // the whole rounds walked as without the tail (the 1x1 + residual layers)

@@ -11,7 +11,10 @@
 // starting there -- so clamping the start into that range reproduces the per-frame edge clamp
 // (generators.py:92-100) for every start.
 //   window_bases        base[b] = seq_b * T_tab + clamp(start_b) - lo; a sequence outside the
-//                       pool is a fault
+//                       pool is a fault.  With frame tables (vp3d_capi.cpp, plan_frame_tables:
+//                       blocks 1 .. d computed once per table row too, level l with its own
+//                       pitch) the bases are those of the deepest level: the same clamp, the
+//                       pitch of that level in place of T_tab, read at j * step_{d+1}
 //   gather_table_rows   the windows' rows copied out of the table into the contiguous
 //                       (B, T_out) layout the expand conv itself writes (kernel forms without
 //                       indirect windows; the bit-identity reference of the tests)

@@ -123,15 +123,18 @@ struct vp3d_handle {
     float* gather_ws = nullptr;
     size_t gather_bytes = 0;
     // expand table of an f16x3 vp3d_forward_windows_pool (forward_impl's table path,
-    // expand_table.hip): one allocation [window bases: B int32, padded | table: n_seq * T_tab
-    // split rows], refilled by every forward that takes the path; tab_pairs: the table's own
+    // expand_table.hip): one allocation of slots [window bases: B int32, padded | table: n_seq *
+    // T_tab split rows] -- one slot, or three rotating through the levels of the frame tables --
+    // refilled by every forward that takes the path; tab_pairs: the table's own
     // pair list (sequence i, the table's first start), kept per sequence count and start; tab_mode: the path the last
-    // gathered forward took (vp3d_expand_table_mode)
+    // gathered forward took (vp3d_expand_table_mode), tab_depth: its frame-table depth
+    // (vp3d_frame_table_depth)
     void* tab_ws = nullptr;
     size_t tab_bytes = 0;
     int32_t* tab_pairs = nullptr;
     std::vector<int32_t> tab_pairs_host;
     int tab_mode = 0;
+    int tab_depth = 0;
     // split-K workspace of conv_gemm_a4 (ConvGemmParams::sk_part / sk_flag), allocated on the
     // first forward whose plan splits a layer; flags zeroed then, each owner unit takes its
     // helpers' counts back out (and vp3d_sync_status re-zeroes them after a reported timeout)

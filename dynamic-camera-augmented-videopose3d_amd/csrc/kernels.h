@@ -102,7 +102,9 @@ hipError_t launch_conv_gemm_a4_x3(const ConvGemmParams& p, bool out_f32, hipStre
 // of the table), instead of at b * T_in; R_T < 0 likewise for the split residual.  Table bytes
 // < 2^31 - 64 KiB (32-bit lane offsets from the table start).  Taken by launch_conv_gemm_a4_x3
 // (split output) where this holds: whole tiles with a half-N / quarter-N tail at most.
-bool conv_gemm_a4_x3_indirect_ok(const ConvGemmParams& p);
+// `any_fill`: without a4's tile-count rule (the block that reads a frame table: a launch of
+// fewer tiles than a4 otherwise takes runs them as one partial round).
+bool conv_gemm_a4_x3_indirect_ok(const ConvGemmParams& p, bool any_fill = false);
 // Split-K tail of an a4 launch (conv_gemm_tail.hip): rows [m_begin, M) as (N / 64) x S
 // K-slices of 256 x 64 over `ncu` CUs, f32 partials in p.sk_part (the split workspace), then
 // one reduction launch with a4's epilogue -- the split-fp16 one (x3) or the 16-bit one (bf16 /
@@ -374,7 +376,8 @@ constexpr unsigned kFaultNonFinite = 2u;
 constexpr unsigned kFaultWindowStart = 4u;
 // expand_table.hip: the table path of an f16x3 vp3d_forward_windows_pool (vp3d_capi.cpp)
 // base[b] = seq_b * T_tab + clamp(start_b, lo, seq_len - 1 + lead) - lo (table row 0 of a
-// sequence = start `lo`)
+// sequence = start `lo`); T_tab = the rows per sequence of the table the bases are for (with
+// frame tables the deepest level's pitch)
 hipError_t launch_window_bases(const int32_t* pairs, const int32_t* seq_len, int B, int n_seq, int T_tab, int lo,
                                int lead, int32_t* base, unsigned* fault, hipStream_t s);
 hipError_t launch_gather_table_rows(const void* table, const int32_t* base, int B, int T_out, int s0,

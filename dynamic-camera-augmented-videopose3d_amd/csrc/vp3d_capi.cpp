@@ -507,9 +507,141 @@ struct TablePlan {
     int b_pad = 0;  // int32 slots of the window bases in front of the table
     size_t table_bytes = 0;
     bool forced = false;  // VP3D_EXPAND_TABLE=1 / copy
+    // Frame tables (mode 1 only): blocks 1 .. depth are computed once per table row as well, level
+    // l = block l's output, one row per frame position.  pitch[l]: rows per sequence of level l
+    // (pitch[0] = T_tab; each level loses its k-conv's reach); step[l]: table rows between
+    // consecutive rows of a window at level l (step[0] = s0).  Block depth + 1 reads level `depth`
+    // through the window bases.
+    int depth = 0;
+    std::vector<int> pitch, step;
+    int max_base = 0;  // the largest row base inside a sequence: clamp(start) - lo <= max_base
+    bool ix_allowed = false;  // indirect windows not ruled out (copy on request, VP3D_GEMM=q64, f32 rows)
 };
 // table rows may number at most 1 / kTableFactor of the window rows they replace
 constexpr int kTableFactor = 2;
+
+// The f16x3 launch geometry of block layer L (k-conv, or 1x1 + residual) computed once per table
+// row: one pseudo-window per sequence at frame stride 1 over the level below -- `pitch_in` rows per
+// sequence, consecutive rows of a window `step` table rows apart -- so tap k of output row q reads
+// row q + k dil step and the residual slice row q + res_off step.  A plain direct launch: the
+// dilated-conv parameters sequence mode runs.
+void table_layer_geometry(ConvGemmParams& p, const Layer& L, int n_seq, int pitch_in, int step) {
+    const int pitch_out = pitch_in - (L.taps - 1) * L.dil * step;
+    p.M = n_seq * pitch_out;
+    p.T_out = pitch_out;
+    p.T_in = pitch_in;
+    p.stride = 1;
+    p.dil = L.dil * step;
+    p.Ktap = 2 * L.cin;  // every tap its own K segment, the K order unchanged
+}
+void table_residual_geometry(ConvGemmParams& p, const Layer& L, int pitch_res, int step) {
+    p.R_T = pitch_res;
+    p.R_stride = 1;
+    p.R_off = L.res_off * step;
+}
+// ... and of block layer L read through the window bases in front of the deepest table (`b_pad`
+// int32 slots): window b's input row j is table row base[b] + j step
+void indirect_layer_geometry(ConvGemmParams& p, const Layer& L, int b_pad, int step) {
+    if (L.residual) {  // the 1x1: its residual slice out of the table
+        p.R_T = -b_pad;
+        p.R_stride = L.res_stride * step;
+        p.R_off = L.res_off * step;
+    } else {  // the k-conv: tap k of output row r at base[b] + (r stride + k dil) step
+        p.T_in = -b_pad;
+        p.stride = L.stride * step;
+        p.dil = L.dil * step;
+        p.Ktap = 2 * L.cin;
+    }
+}
+// the sizes, pitches and (stand-in) pointers of an f16x3 block layer for the eligibility rules
+ConvGemmParams x3_probe(const Layer& L, int M, int T_out, int T_in) {
+    void* const al = (void*)(uintptr_t)256;  // (the pointers only stand for their alignment)
+    ConvGemmParams q{};
+    q.A = q.W = al;
+    q.Y = al;
+    q.M = M;
+    q.N = L.cout;
+    q.K = L.K;
+    q.Kp = 2 * L.Kp;
+    q.T_out = T_out;
+    q.T_in = T_in;
+    q.stride = L.stride;
+    q.dil = L.dil;
+    q.Ktap = 2 * L.Ktap;
+    q.lda = 2 * L.cin;
+    q.ldy = 2 * L.cout;
+    q.relu = 1;
+    if (L.residual) {
+        q.R = al;
+        q.ldr = 2 * L.cout;
+        q.R_stride = L.res_stride;
+        q.R_off = L.res_off;
+    }
+    return q;
+}
+
+// The frame-table depth of a forward whose expand table passed its own rules (tp.mode != 0, indirect
+// windows not ruled out): the deepest d <= blocks - 1 (and <= VP3D_FRAME_TABLES, which also lifts
+// the size rule) such that at every level 1 .. d the table a block reads has at most
+// 1 / kTableFactor of that block's window rows and both its launches run a4's whole / half-N /
+// quarter-N tiles (eligible without the split workspace: no split-K plan, no split-K tail, never
+// q64), and both layers of block d + 1 take indirect windows; a level whose consumer does not is
+// passed over for the next shallower one that does, down to depth 0 = plan_expand_table's own
+// choice.  Every table is smaller than level 0's, so the 2 GiB rule holds for all.  Fills
+// tp.depth / pitch / step, and makes the plan an indirect one (mode 1) for a depth >= 1.
+void plan_frame_tables(const vp3d_handle* h, int B, const std::vector<int>& len, int n_seq, TablePlan& tp) {
+    tp.depth = 0;
+    tp.pitch.assign(1, tp.T_tab);
+    tp.step.assign(1, tp.s0);
+    if (tp.mode == 0 || !tp.ix_allowed) return;
+    const int nl = (int)h->layers.size();
+    int want = (nl - 2) / 2 - 1;  // the last block and the shrink always run per window
+    bool force = false;
+    if (const char* e = getenv("VP3D_FRAME_TABLES")) {
+        want = std::min(want, std::max(0, atoi(e)));
+        force = true;
+    }
+    const int C = h->layers[0].cout;
+    int ok_depth = 0;  // the deepest level whose consumer block takes indirect windows
+    for (int l = 1; l <= want; ++l) {
+        const Layer &Lk = h->layers[2 * l - 1], &Lp = h->layers[2 * l];
+        const int pin = tp.pitch[l - 1], st = tp.step[l - 1];
+        const int pout = pin - (Lk.taps - 1) * Lk.dil * st;
+        if (!Lk.relu || Lk.residual || !Lp.relu || !Lp.residual || Lp.taps != 1 || Lp.stride != 1 ||
+            Lp.res_stride != Lk.stride || Lk.cin != C || Lk.cout != C || Lp.cout != C || pout <= 0)
+            break;
+        // the last row a window reads at this level lies inside its sequence's rows
+        if ((int64_t)tp.max_base + (int64_t)(len[2 * l] - 1) * st * Lk.stride >= pout) break;
+        if (!force && (int64_t)n_seq * pin > (int64_t)B * len[2 * l - 1] / kTableFactor) break;
+        ConvGemmParams q = x3_probe(Lk, 0, 0, 0);
+        table_layer_geometry(q, Lk, n_seq, pin, st);
+        ConvGemmParams r = x3_probe(Lp, 0, 0, 0);
+        table_layer_geometry(r, Lp, n_seq, pout, st);
+        table_residual_geometry(r, Lp, pin, st);
+        if (!vp3d::conv_gemm_a4_x3_eligible(q, false) || !vp3d::conv_gemm_a4_x3_eligible(r, false)) break;
+        tp.pitch.push_back(pout);
+        tp.step.push_back(st * Lk.stride);
+        // block l + 1 over this level's table (the 1x1 of the last block may write f32 rows for
+        // the f32 shrink: not an indirect form)
+        const Layer &Nk = h->layers[2 * l + 1], &Np = h->layers[2 * l + 2];
+        if (nl - 2 == 2 * l + 2 && !x3_split_shrink(h)) continue;
+        ConvGemmParams ck = x3_probe(Nk, B * len[2 * l + 1], len[2 * l + 1], 0);
+        indirect_layer_geometry(ck, Nk, tp.b_pad, tp.step[l]);
+        ConvGemmParams cp = x3_probe(Np, B * len[2 * l + 2], len[2 * l + 2], len[2 * l + 1]);
+        indirect_layer_geometry(cp, Np, tp.b_pad, tp.step[l]);
+        // (a4 at any tile count: no other kernel reads a table, and a partial round of whole
+        // tiles is little against the block rows the tables above it save)
+        if (Nk.relu && !Nk.residual && Np.relu && Np.residual && vp3d::conv_gemm_a4_x3_indirect_ok(ck, true) &&
+            vp3d::conv_gemm_a4_x3_indirect_ok(cp, true))
+            ok_depth = l;
+    }
+    tp.depth = ok_depth;
+    tp.pitch.resize(ok_depth + 1);
+    tp.step.resize(ok_depth + 1);
+    // block 1 on the table needs no indirect form of its own: the table path whatever
+    // plan_expand_table found for the per-window block 1
+    if (ok_depth >= 1) tp.mode = 1;
+}
 
 TablePlan plan_expand_table(const vp3d_handle* h, int B, const std::vector<int>& len, int dtype, const GatherSrc* gs,
                             int n_seq, int max_len) {
@@ -519,6 +651,9 @@ TablePlan plan_expand_table(const vp3d_handle* h, int B, const std::vector<int>&
     const char* e = getenv("VP3D_EXPAND_TABLE");
     if (e && e[0] == '0') return tp;
     const bool force = e && (strcmp(e, "1") == 0 || strcmp(e, "copy") == 0);
+    // a forced frame-table depth >= 1 (plan_frame_tables) needs the level-0 table under it
+    const char* fe = getenv("VP3D_FRAME_TABLES");
+    const bool force_size = force || (fe && atoi(fe) >= 1);
     const Layer& L0 = h->layers[0];
     const int C = L0.cout;
     tp.s0 = L0.stride;
@@ -533,8 +668,9 @@ TablePlan plan_expand_table(const vp3d_handle* h, int B, const std::vector<int>&
     // 32-bit lane offsets from the table start (conv_gemm_a4), some slack for the tiles' rebased
     // resources; one rule for both table modes
     if (bytes >= ((int64_t)1 << 31) - 65536) return tp;
-    if (!force && rows > (int64_t)B * len[0] / kTableFactor) return tp;
+    if (!force_size && rows > (int64_t)B * len[0] / kTableFactor) return tp;
     tp.T_tab = (int)t_tab;
+    tp.max_base = max_len - 1 + gs->lead - tp.lo;
     tp.table_bytes = (size_t)bytes;
     tp.b_pad = (B + 63) / 64 * 64;
     tp.mode = 2;
@@ -545,51 +681,26 @@ TablePlan plan_expand_table(const vp3d_handle* h, int B, const std::vector<int>&
     const char* ge = getenv("VP3D_GEMM");
     if (ge && strcmp(ge, "q64") == 0) return tp;
     if (nl - 2 == 2 && !x3_split_shrink(h)) return tp;  // (the 1x1 would write f32 rows)
-    void* const al = (void*)(uintptr_t)256;
+    tp.ix_allowed = true;
     const Layer &L1 = h->layers[1], &L2 = h->layers[2];
-    ConvGemmParams q{};
-    q.A = q.W = al;
-    q.Y = al;
-    q.M = B * len[1];
-    q.N = L1.cout;
-    q.K = L1.K;
-    q.Kp = 2 * L1.Kp;
-    q.T_out = len[1];
-    q.T_in = -tp.b_pad;
-    q.stride = L1.stride * tp.s0;
-    q.dil = L1.dil * tp.s0;
-    q.Ktap = 2 * L1.cin;
-    q.lda = 2 * L1.cin;
-    q.ldy = 2 * L1.cout;
-    q.relu = 1;
+    ConvGemmParams q = x3_probe(L1, B * len[1], len[1], 0);
+    indirect_layer_geometry(q, L1, tp.b_pad, tp.s0);
     if (!L1.relu || L1.residual || !vp3d::conv_gemm_a4_x3_indirect_ok(q)) return tp;
-    ConvGemmParams r{};
-    r.A = r.W = al;
-    r.Y = al;
-    r.R = al;
-    r.M = B * len[2];
-    r.N = L2.cout;
-    r.K = L2.K;
-    r.Kp = 2 * L2.Kp;
-    r.T_out = len[2];
-    r.T_in = len[1];
-    r.stride = L2.stride;
-    r.dil = L2.dil;
-    r.Ktap = 2 * L2.Ktap;
-    r.lda = 2 * L2.cin;
-    r.ldy = 2 * L2.cout;
-    r.ldr = 2 * L2.cout;
-    r.R_T = -tp.b_pad;
-    r.relu = 1;
+    ConvGemmParams r = x3_probe(L2, B * len[2], len[2], len[1]);
+    indirect_layer_geometry(r, L2, tp.b_pad, tp.s0);
     if (!L2.relu || !L2.residual || !vp3d::conv_gemm_a4_x3_indirect_ok(r)) return tp;
     tp.mode = 1;
     return tp;
 }
 
-// the table allocation ([bases | table]) and the table's own pair list
+// one table slot: [bases | table]; b_pad % 64 == 0 and whole 16-byte rows keep every slot aligned
+size_t table_slot_bytes(const TablePlan& tp) { return (size_t)tp.b_pad * 4 + tp.table_bytes; }
+
+// the table allocation (one slot; with frame tables three, rotating through the levels as block
+// input, k-conv output and 1x1 output, each the size of level 0) and the table's own pair list
 int ensure_table(vp3d_handle* h, const TablePlan& tp, int n_seq, hipStream_t s) {
     const bool same_pairs = (int)h->tab_pairs_host.size() == 2 * n_seq && (n_seq == 0 || h->tab_pairs_host[1] == tp.lo);
-    const size_t need = (size_t)tp.b_pad * 4 + tp.table_bytes;
+    const size_t need = table_slot_bytes(tp) * (tp.depth > 0 ? 3 : 1);
     if (need > h->tab_bytes) {
         if (h->tab_ws) HIP_TRY(hipFree(h->tab_ws));
         h->tab_ws = nullptr;
@@ -763,6 +874,8 @@ static int forward_impl(vp3d_handle* h, const float* x, int B, int T, float* y, 
     // the expand table path (f16x3, gathered, sizes only); with indirect windows the expand
     // output never exists per window, so the buffers hold block 1's rows at most
     TablePlan tp = plan_expand_table(h, B, len, dtype, gs, n_seq, max_len);
+    // frame tables: blocks 1 .. depth once per table row too, block depth + 1 the first per window
+    plan_frame_tables(h, B, len, n_seq, tp);
     // the copy form costs more than the expand conv it replaces (it writes the same rows after
     // filling the table): only on request, never as the automatic choice
     if (tp.mode == 2 && !tp.forced) tp = TablePlan{};
@@ -792,8 +905,11 @@ static int forward_impl(vp3d_handle* h, const float* x, int B, int T, float* y, 
         const char* xe = getenv("VP3D_X3_EXPAND");
         if ((xe && strcmp(xe, "pack") == 0) || !expand_gemm_x3_eligible(tab_p, &tab_gs)) tp = TablePlan{};
     }
-    if (gs) h->tab_mode = tp.mode;
-    const int buf_first = tp.mode == 1 ? 1 : 0;
+    if (gs) {
+        h->tab_mode = tp.mode;
+        h->tab_depth = tp.depth;
+    }
+    const int buf_first = tp.mode == 1 ? 2 * tp.depth + 1 : 0;
     int rc = ensure_ws(h, B, T, dtype, buf_first);
     if (rc) return rc;
 
@@ -805,6 +921,10 @@ static int forward_impl(vp3d_handle* h, const float* x, int B, int T, float* y, 
         tab_gs.pairs = h->tab_pairs;
         tab_p.Y = table;
     }
+    // the table slots' tables (level 0 in slot 0; slots 1 and 2 only with frame tables)
+    void* tbuf[3] = {table, nullptr, nullptr};
+    if (tp.depth > 0)
+        for (int i = 1; i < 3; ++i) tbuf[i] = table + i * table_slot_bytes(tp);
     const Act act = dtype == VP3D_DTYPE_F32 ? Act::F32 : (dtype == VP3D_DTYPE_BF16 ? Act::BF16 : Act::F16);
     const size_t es = esize(dtype);
     const size_t buf_elems = (size_t)B * len[buf_first] * h->cfg.channels;
@@ -839,17 +959,23 @@ static int forward_impl(vp3d_handle* h, const float* x, int B, int T, float* y, 
         p.ldy = L.cout;
         p.W = dtype == VP3D_DTYPE_F32 ? (const void*)L.w32
                                       : (dtype == VP3D_DTYPE_BF16 ? (const void*)L.wbf : (const void*)L.wh);
+        // frame tables: the level (block) this layer builds once per table row, 0 = per window;
+        // `ilevel`: the level block tp.depth + 1 reads through the window bases, else -1
+        const int tlevel = tp.mode == 1 && li >= 1 && li <= 2 * tp.depth ? (li + 1) / 2 : 0;
+        const int ilevel = tp.mode == 1 && (li == 2 * tp.depth + 1 || li == 2 * tp.depth + 2) ? tp.depth : -1;
         int out_buf = -1;
         if (last) {
             p.Y = y;
         } else {
-            // pick a buffer that is neither the current input nor the block input
+            // pick a buffer (a table slot for a table level) that is neither the current input
+            // nor the block input
+            void* const* const bufs = tlevel ? tbuf : buf;
             for (int bi = 0; bi < 3; ++bi) {
-                if (buf[bi] == cur_in || buf[bi] == block_in) continue;
+                if (bufs[bi] == cur_in || bufs[bi] == block_in) continue;
                 out_buf = bi;
                 break;
             }
-            p.Y = buf[out_buf];
+            p.Y = bufs[out_buf];
         }
         if (L.residual) {
             p.R = block_in;
@@ -857,6 +983,13 @@ static int forward_impl(vp3d_handle* h, const float* x, int B, int T, float* y, 
             p.R_stride = L.res_stride;
             p.R_off = L.res_off;
             p.ldr = L.cout;
+        }
+        if (tlevel) {
+            // (cur_len / block_len are table pitches here)
+            table_layer_geometry(p, L, n_seq, cur_len, tp.step[tlevel - 1]);
+            if (L.residual) table_residual_geometry(p, L, block_len, tp.step[tlevel - 1]);
+        } else if (first && tp.mode) {
+            p.M = tab_p.M;  // (the FLOP of the launch made: the table's fill)
         }
         // algorithmic FLOP of the layer (unpadded K), timed from before any packing
         ProfEvent pe{};
@@ -897,7 +1030,8 @@ static int forward_impl(vp3d_handle* h, const float* x, int B, int T, float* y, 
             // either nothing more (block 1 reads the table through them) or the windows' rows
             // copied out into the layout the per-window expand writes
             e = launch_expand_gemm_x3(tab_p, &tab_gs, s);
-            if (e == hipSuccess)
+            // (with frame tables the bases go in front of the deepest level, after its launch)
+            if (e == hipSuccess && tp.depth == 0)
                 e = launch_window_bases(gs->pairs, gs->seq_len, B, n_seq, tp.T_tab, tp.lo, gs->lead, (int32_t*)h->tab_ws,
                                         h->sk_err_dev, s);
             if (e == hipSuccess && tp.mode == 2)
@@ -940,30 +1074,38 @@ static int forward_impl(vp3d_handle* h, const float* x, int B, int T, float* y, 
                 p.lda = 2 * L.cin;
                 p.Ktap = 2 * L.Ktap;
             }
-            if (tp.mode == 1 && li == 1) {
-                // block 1's k-conv over the table: window b's input row j is table row
-                // base[b] + j s0, so tap k of output row r sits at base[b] + (r stride + k dil) s0
-                // -- every tap its own K segment, the K order unchanged
-                p.T_in = -tp.b_pad;
-                p.stride = L.stride * tp.s0;
-                p.dil = L.dil * tp.s0;
-                p.Ktap = 2 * L.cin;
-            }
+            // the first per-window block's k-conv over the deepest table: window b's input row j
+            // is table row base[b] + j step, so tap k of output row r sits at
+            // base[b] + (r stride + k dil) step -- every tap its own K segment, the K order unchanged
+            if (ilevel >= 0 && !L.residual) indirect_layer_geometry(p, L, tp.b_pad, tp.step[ilevel]);
+            if (tlevel) p.Ktap = 2 * L.cin;
             const bool out_f32 = li == nl - 2 && !x3_split_shrink(h);
             p.Kp = 2 * L.Kp;
             p.W = L.wx3;
             p.scale = L.scale_x3;
             p.ldy = out_f32 ? L.cout : 2 * L.cout;
             if (L.residual) p.ldr = 2 * L.cout;
-            if (tp.mode == 1 && li == 2) {  // block 1's residual slice, out of the table
-                p.R_T = -tp.b_pad;
-                p.R_stride = L.res_stride * tp.s0;
-                p.R_off = L.res_off * tp.s0;
-            }
+            // that block's residual slice, out of the table
+            if (ilevel >= 0 && L.residual) indirect_layer_geometry(p, L, tp.b_pad, tp.step[ilevel]);
             // the one-wave-per-SIMD kernel where it fills the chip (VP3D_GEMM=q64 forces q64)
             const char* ge = getenv("VP3D_GEMM");
-            if ((rc = attach_split_ws(h, p, s))) return rc;
-            if (!(ge && strcmp(ge, "q64") == 0) && conv_gemm_a4_x3_eligible(p, out_f32)) {
+            if (tlevel) {
+                // a table row must come from the per-row instruction chain of the window row it
+                // replaces: a4's whole / half-N / quarter-N tiles only.  No split workspace is
+                // attached, so neither a split-K plan nor the split-K tail is planned (also
+                // under VP3D_A4_SPLIT=2), and q64 is never the fallback (plan_frame_tables)
+                if (out_f32 || !conv_gemm_a4_x3_eligible(p, false))
+                    return fail(VP3D_ERR_ASSERT, "frame table layer " + std::to_string(li) + " left the a4 tile forms");
+                e = launch_conv_gemm_a4_x3(p, false, s);
+                // after the deepest level: the windows' bases in front of it, at its pitch
+                if (e == hipSuccess && li == 2 * tp.depth)
+                    e = launch_window_bases(gs->pairs, gs->seq_len, B, n_seq, p.T_out, tp.lo, gs->lead,
+                                            (int32_t*)p.Y - tp.b_pad, h->sk_err_dev, s);
+            } else if ((rc = attach_split_ws(h, p, s))) {
+                return rc;
+            } else if (!(ge && strcmp(ge, "q64") == 0) &&
+                       (conv_gemm_a4_x3_eligible(p, out_f32) || (ilevel >= 1 && !out_f32))) {
+                // (the block over a frame table: a4 at any tile count, plan_frame_tables)
                 e = launch_conv_gemm_a4_x3(p, out_f32, s);
             } else {
                 if (!conv_gemm_q64_x3_eligible(p, out_f32)) return fail(VP3D_ERR_ARG, x3_requirement());
@@ -1041,7 +1183,7 @@ static int forward_impl(vp3d_handle* h, const float* x, int B, int T, float* y, 
             block_len = cur_len;
         }
         cur_in = p.Y;
-        cur_len = len[li];
+        cur_len = tlevel ? p.T_out : (first && tp.mode == 1 ? tp.T_tab : len[li]);
         (void)xin_buf;
     }
     if (x3) {
@@ -1115,6 +1257,8 @@ int vp3d_forward_windows_pool(vp3d_handle* h, const float* kps, int32_t f2, cons
 }
 
 int vp3d_expand_table_mode(const vp3d_handle* h) { return h ? h->tab_mode : -1; }
+
+int vp3d_frame_table_depth(const vp3d_handle* h) { return h ? h->tab_depth : -1; }
 
 int vp3d_sync_status(vp3d_handle* h, void* stream) {
     if (!h) return fail(VP3D_ERR_ARG, "handle is NULL");

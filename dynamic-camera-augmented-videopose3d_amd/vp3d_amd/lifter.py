@@ -121,7 +121,15 @@ class NativeLifter:
         range guard sees every resident frame of `seqs`, and a pair naming a sequence outside
         `seqs` is a fault (RuntimeError at the next forward or sync_status); starts outside their
         sequence are edge-clamped as on every path.  VP3D_EXPAND_TABLE=0 keeps the per-window expand; expand_table_mode() tells
-        which path the last call took."""
+        which path the last call took.
+
+        Frame tables: with the expand table, blocks 1 .. d are computed once per resident frame
+        position as well, as long as the table a block reads has at most half that block's
+        window rows (d <= blocks - 1; the first per-window block reads the deepest table through
+        the same row bases): still the same poses, bit for bit.  The range guard then sees every
+        table row of every level.  VP3D_FRAME_TABLES=<d> forces a depth (0 = the expand table
+        only; clamped to what the kernels' conditions allow); frame_table_depth() tells the
+        depth the last call took."""
         def _idx(d):
             d = torch.device(d)
             return (d.type, d.index if d.index is not None else torch.cuda.current_device())
@@ -154,6 +162,11 @@ class NativeLifter:
         expand table read by block 1 through indirect rows, 2 = the table with the windows' rows
         copied out (vp3d_expand_table_mode)."""
         return self._lib.vp3d_expand_table_mode(self._h)
+
+    def frame_table_depth(self) -> int:
+        """The frame-table depth of the last forward_windows: how many blocks were computed once
+        per table row instead of once per window row, 0 = none (vp3d_frame_table_depth)."""
+        return self._lib.vp3d_frame_table_depth(self._h)
 
     # ---- f16x3 activation pre-scale ----
     def set_x3_prescale(self, p) -> None:

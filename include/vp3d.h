@@ -162,9 +162,24 @@ int vp3d_forward_windows(vp3d_handle* h, const float* kps, int32_t f2, const flo
  * batches over a resident set qualify; a training-size batch over a large set never does.
  * VP3D_EXPAND_TABLE (read once per forward): 0 = never, 1 = whenever the table fits 2 GiB,
  * copy = the table, then the windows' rows copied out of it for block 1 (also what block-1
- * kernel forms without indirect rows get).  What differs from vp3d_forward_windows on this path:
- *   - the f16x3 range guard (vp3d_sync_status) sees every frame of the n_seq sequences, not
- *     only the frames some window uses: one non-finite resident frame faults the forward;
+ * kernel forms without indirect rows get).
+ * Frame tables: the same holds below the point where windows stop overlapping -- row j of block
+ * b's output in the window starting at frame s depends on the sequence and on frame position
+ * s + step j alone -- so with the expand table read through indirect rows, blocks 1 .. d are
+ * computed once per table row as well (one dilated launch per layer over the level below, three
+ * table-sized buffers rotating), and block d + 1 is the first per-window block, reading level d
+ * through the window bases.  The depth d is the deepest, at most blocks - 1, for which at every
+ * level the table a block reads has at most half that block's window rows, its launches run
+ * conv_gemm_a4's whole / half-N / quarter-N tiles (never a split-K form: every table row keeps the
+ * K order of the window row it replaces) and block d + 1 reads indirect rows; the poses are the
+ * same bits at every depth.  VP3D_FRAME_TABLES=<d> (read once per forward) forces a depth, also
+ * past the size rule, clamped to what the other conditions allow: 0 = the expand table only, d >= 1
+ * takes the expand table with it unless VP3D_EXPAND_TABLE is 0 or copy.
+ * What differs from vp3d_forward_windows on this path:
+ *   - the f16x3 range guard (vp3d_sync_status) sees every frame of the n_seq sequences -- every
+ *     table row of every level -- not only the frames some window uses: one non-finite
+ *     resident frame, or an activation past the f16 range at a frame position no window
+ *     reads, faults the forward;
  *   - a pair naming a sequence outside [0, n_seq) is a fault reported by vp3d_sync_status /
  *     the next forward (window starts outside their sequence are edge-clamped as ever). */
 int vp3d_forward_windows_pool(vp3d_handle* h, const float* kps, int32_t f2, const float* cams,
@@ -175,6 +190,9 @@ int vp3d_forward_windows_pool(vp3d_handle* h, const float* kps, int32_t f2, cons
  * expand table read by block 1 through indirect rows, 2 = the table with the windows' rows
  * copied out.  -1 for a NULL handle.  (Diagnostics and tests.) */
 int vp3d_expand_table_mode(const vp3d_handle* h);
+/* The frame-table depth of the handle's last gathered forward: the blocks computed once per table
+ * row (0 = none: the expand table at most).  -1 for a NULL handle.  (Diagnostics and tests.) */
+int vp3d_frame_table_depth(const vp3d_handle* h);
 
 /* ---- f16x3 activation pre-scale (opt-in; no reference counterpart) ----
  * The split-fp16 path stores every activation as hi = f16(a), lo = f16(a - hi); lo is an f16
