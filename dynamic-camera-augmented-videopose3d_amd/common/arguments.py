@@ -101,6 +101,11 @@ def build_parser():
            '(the reference hard-codes /vol/bitbucket/bw1222/data/npz)')
     a('--compute-dtype', default='fp32', choices=['fp32', 'f16x3', 'bf16', 'fp16'],
       help='arithmetic of the conv stack (fp32 = parity path; f16x3 = split fp16, fp32-level results on the 16-bit MFMAs)')
+    a('--train-dtype', default='fp32', choices=['fp32', 'bf16'],
+      help='precision of the training step: fp32, or bf16 mixed precision (the block convolutions on bf16 '
+           'operands with f32 accumulation; f32 master weights, BatchNorm and Adam).  The per-epoch evaluation '
+           'keeps --compute-dtype.  Whether a bf16-trained checkpoint reaches the fp32 one\'s MPJPE on real '
+           'data has not been measured')
     a('--x3-calibrate', default=0, type=int, metavar='N',
       help='with --evaluate and --compute-dtype f16x3: choose the exact power-of-two activation pre-scale '
            'of the f16x3 path on the first N frames of the first evaluated sequence (0 = off)')
@@ -122,6 +127,8 @@ def parse_args(argv=None):
     # reference :97-105
     if args.resume and args.evaluate:
         ap.error('--resume and --evaluate cannot be set at the same time')
+    if args.evaluate and args.train_dtype != 'fp32':
+        ap.error('--train-dtype sets the precision of training; with --evaluate use --compute-dtype')
     if args.export_training_curves and args.no_eval:
         ap.error('--export-training-curves and --no-eval cannot be set at the same time')
     if args.dataset not in DATASETS:

@@ -90,6 +90,7 @@ class TemporalModelBase(nn.Module):
         self.shrink = nn.Conv1d(channels, num_joints_out * 3, 1)
 
         self.compute_dtype = 'fp32'
+        self.train_dtype = 'fp32'
         self._lifter = None
         self._lifter_key = None
         self._trainer = None
@@ -139,6 +140,22 @@ class TemporalModelBase(nn.Module):
         if dtype not in _N.DTYPES:
             raise ValueError(f"unknown compute dtype {dtype!r}")
         self.compute_dtype = dtype
+        return self
+
+    def set_train_dtype(self, dtype):
+        """Precision of the train-mode step: 'fp32' (default: every GEMM on the exact-f32 MFMA) or
+        'bf16' (mixed precision: the block convolutions' forward, data-gradient and
+        weight-gradient GEMMs take bf16 operands with f32 accumulation; the expand conv, the
+        shrink, BatchNorm, the element-wise passes, the gradients, the parameters and the
+        optimiser state stay f32).  fp16 and f16x3 are refused: the gradients of a mean-over-batch
+        MPJPE lie below f16's range, so they would need loss scaling.  Independent of
+        set_compute_dtype (eval only); a plain attribute, so state_dict keys are unchanged and
+        checkpoints interchange between the modes.  Whether a bf16-trained checkpoint reaches the
+        fp32 one's MPJPE on real data has not been measured."""
+        if dtype not in NativeTrainer.TRAIN_DTYPES:
+            raise ValueError(f"unknown training dtype {dtype!r}: 'fp32' or 'bf16' (fp16 / f16x3 training "
+                             "would need loss scaling)")
+        self.train_dtype = dtype
         return self
 
     # ---- native engine -------------------------------------------------------------
@@ -252,6 +269,9 @@ class TemporalModelBase(nn.Module):
     def _train_forward(self, x):
         """Train-mode forward through the native trainer (TemporalModel.py:62-76, :126-138 /
         :188-198 with BatchNorm1d in training mode and nn.Dropout active)."""
+        if self.train_dtype == 'bf16' and self.channels % 8 != 0:
+            raise ValueError(f"vp3d: bf16 training needs channels % 8 == 0 (got {self.channels}): the 16-bit "
+                             "operand rows are read 8 elements at a time")
         bns = [self.expand_bn, *self.layers_bn]
         momentum = bns[0].momentum
         if any(bn.momentum != momentum for bn in bns):
@@ -276,7 +296,9 @@ class TemporalModelBase(nn.Module):
                 raise RuntimeError("vp3d: parameters must be contiguous float32 tensors on the input's device")
         trainable = tuple(isinstance(t, nn.Parameter) and t.requires_grad for t in tensors)
         trainer = self.native_trainer(x.device)
-        seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if self.drop.p > 0 else 0
+        if trainer.compute != self.train_dtype:
+            trainer.set_compute(self.train_dtype)
+        seed =int(torch.randint(0, 2 ** 62, (1,)).item()) if self.drop.p > 0 else 0
         x = x.contiguous().float()
         return TrainStep.apply(trainer, float(self.drop.p), float(factor), seed, T_out, trainable, x, *tensors)
 

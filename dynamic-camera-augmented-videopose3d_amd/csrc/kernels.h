@@ -406,10 +406,11 @@ hipError_t launch_act_stats(const float* a, int64_t n, ActStats* out, hipStream_
 
 // ---- training step (train.hip, vp3d_train.cpp) ----
 // weight gradient of one conv: part[s][n][k] over row splits s (TN GEMM over rows)
+// (dZ and X: f32 rows for wgrad_f32_kernel, bf16 rows for wgrad_bf16_kernel; ldz / cin in elements)
 struct WgradParams {
-    const float* dZ;   // output-gradient rows; row of (b, t) = b*dz_T + t + dz_off, ldz floats each
+    const void* dZ;    // output-gradient rows; row of (b, t) = b*dz_T + t + dz_off, ldz elements each
     int ldz, dz_T, dz_off;
-    const float* X;    // layer input rows (cin floats); tap row = b*T_in + t*stride + tap*dil
+    const void* X;     // layer input rows (cin elements); tap row = b*T_in + t*stride + tap*dil
     int cin, T_in, stride, dil, T_out;
     int64_t M;         // B * T_out
     int N, K;          // cout, taps * cin
@@ -436,22 +437,33 @@ int64_t train_reduce_chunks(int64_t M, int C);  // row chunks a reduction over e
 // mode 0: forward [cout][k*cin+c]; 1: flipped-tap dgrad [cin][(taps-1-k)*cout+o]; 2: [k*cin+c][cout]
 hipError_t launch_pack_weights(const float* w, int cout, int cin, int taps, int mode, int Kp, float* out,
                                hipStream_t s);
+// the same layouts with the values rounded to bf16 (nearest even); `out` [Np][Kp] bf16, zero padded
+hipError_t launch_pack_weights_bf16(const float* w, int cout, int cin, int taps, int mode, int Kp, void* out,
+                                    hipStream_t s);
 hipError_t launch_bn_train_stats(const float* Z, int64_t M, int C, double* part, const float* gamma,
                                  const float* beta, float eps, double momentum, float* running_mean,
                                  float* running_var, float* mean, float* invstd, float* alpha, float* shift,
                                  hipStream_t s);
 hipError_t launch_bn_act_fwd(const float* Z, int64_t M, int C, const float* alpha, const float* shift, float p,
                              uint64_t seed, int layer, const float* R, int T_out, int R_T, int R_stride, int R_off,
-                             float* Y, hipStream_t s);
+                             float* Y, void* Y16, hipStream_t s);
 hipError_t launch_bn_train_backward(const float* dO, const float* Z, int64_t M, int C, const float* gamma,
                                     const float* alpha, const float* shift, const float* mean, const float* invstd,
                                     float p, uint64_t seed, int layer, double* part, float* coef, float* dgamma,
-                                    float* dbeta, int T_out, int dz_T, int dz_off, float* dZ, hipStream_t s);
+                                    float* dbeta, int T_out, int dz_T, int dz_off, float* dZ, void* dZ16,
+                                    hipStream_t s);
 hipError_t launch_colsum(const float* D, int64_t M, int C, int ld, double* part, float* out, hipStream_t s);
 hipError_t launch_res_grad_add(float* dIn, const float* dOut, int64_t M, int C, int T_out, int T_in, int rs, int ro,
                                hipStream_t s);
 int wgrad_splits(int64_t M, int N, int K, int64_t max_part_floats);
-hipError_t launch_wgrad(const WgradParams& p, int S, int taps, float* dW, hipStream_t s);
+// bf16_rows: dZ / X are bf16 rows (N % 8 == 0, cin % 8 == 0, 16-byte aligned) on wgrad_bf16_kernel
+hipError_t launch_wgrad(const WgradParams& p, int S, int taps, float* dW, hipStream_t s, bool bf16_rows = false);
+// train_bf16.hip: the partial tiles of launch_wgrad's bf16 form (sets rows_per_split itself)
+hipError_t launch_wgrad_bf16_tiles(const WgradParams& p, int S, hipStream_t s);
+// test hooks (vp3d_train_read): rows of (b, t) at src row b*src_T + t + src_off widened / copied to
+// dense f32 rows out[(b*T_out + t)][C]
+hipError_t launch_rows_to_f32(const void* src, bool src_bf16, int64_t M, int C, int T_out, int src_T, int src_off,
+                              float* out, hipStream_t s);
 hipError_t launch_adam(const AdamList& L, const AdamHyper& hp, hipStream_t s);
 hipError_t launch_dropout_mask(uint64_t seed, float p, int layer, int64_t n, uint8_t* out, hipStream_t s);
 hipError_t launch_relu_mask(const float* Z, int64_t n, int C, const float* alpha, const float* shift, uint8_t* out,

@@ -22,6 +22,12 @@ namespace vp3d {
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+
+// round to nearest even, as the conv GEMMs' cast-on-load does (gemm::pack8)
+__device__ __forceinline__ bf16x4 to_bf16x4(f32x4 v) {
+    return bf16x4{(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
+}
 
 // ---------------------------------------------------------------------------
 // dropout keep mask: counter-based (splitmix64 of seed, layer, element), so the
@@ -38,8 +44,9 @@ __device__ __forceinline__ bool drop_keep(uint64_t seed, int layer, int64_t idx,
 // ---------------------------------------------------------------------------
 // weight packing (per step: the optimiser changes the torch-layout weights)
 // ---------------------------------------------------------------------------
+template <typename OT>
 __global__ void pack_weights_kernel(const float* __restrict__ w, int cout, int cin, int taps, int mode, int Kp,
-                                    float* __restrict__ out) {
+                                    OT* __restrict__ out) {
     const int64_t total = (int64_t)cout * cin * taps;
     for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < total;
          e += (int64_t)gridDim.x * blockDim.x) {
@@ -54,7 +61,7 @@ __global__ void pack_weights_kernel(const float* __restrict__ w, int cout, int c
             dst = (int64_t)c * Kp + (int64_t)(taps - 1 - k) * cout + o;
         else  // dgrad, non-overlapping taps (strided / 1x1): [k*cin + c][o]
             dst = ((int64_t)k * cin + c) * Kp + o;
-        out[dst] = w[e];
+        out[dst] = (OT)w[e];  // bf16: round to nearest even
     }
 }
 
@@ -199,13 +206,16 @@ __global__ void colsum_finalize_kernel(const double* __restrict__ part, int nchu
 // ---------------------------------------------------------------------------
 // elementwise passes (float4 over channels; C % 4 == 0)
 // ---------------------------------------------------------------------------
-// out = [R[res(m)] +] dropout(relu(z * alpha + shift))
+// out = [R[res(m)] +] dropout(relu(z * alpha + shift));  H16: also Y16 = bf16(out), the operand rows
+// of the next conv in bf16 mode
+template <bool H16>
 __global__ __launch_bounds__(256) void bn_act_fwd_kernel(const float* __restrict__ Z, int64_t M, int C,
                                                          const float* __restrict__ alpha,
                                                          const float* __restrict__ shift, float dscale,
                                                          uint64_t seed, uint64_t thresh, int layer,
                                                          const float* __restrict__ R, int T_out, int R_T,
-                                                         int R_stride, int R_off, float* __restrict__ Y) {
+                                                         int R_stride, int R_off, float* __restrict__ Y,
+                                                         __bf16* __restrict__ Y16) {
     const int c4 = C >> 2;
     const int64_t total = M * c4;
     const bool small = total < INT32_MAX;  // 32-bit row / frame arithmetic
@@ -232,10 +242,13 @@ __global__ __launch_bounds__(256) void bn_act_fwd_kernel(const float* __restrict
             for (int j = 0; j < 4; ++j) o[j] = r[j] + o[j];
         }
         *(f32x4*)(Y + m * C + c) = o;
+        if constexpr (H16) *(bf16x4*)(Y16 + m * C + c) = to_bf16x4(o);
     }
 }
 
-// dz rows (optionally into a zero-padded row layout: row(m) = b*dz_T + t + dz_off)
+// dz rows (optionally into a zero-padded row layout: row(m) = b*dz_T + t + dz_off) as f32 rows (F32),
+// as bf16 rows (H16: the operands of the bf16 dgrad and wgrad) or both
+template <bool F32, bool H16>
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restrict__ dO,
                                                            const float* __restrict__ Z, int64_t M, int C,
                                                            const float* __restrict__ alpha,
@@ -243,7 +256,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
                                                            const float* __restrict__ mean,
                                                            const float* __restrict__ coef, float dscale,
                                                            uint64_t seed, uint64_t thresh, int layer, int T_out,
-                                                           int dz_T, int dz_off, float* __restrict__ dZ) {
+                                                           int dz_T, int dz_off, float* __restrict__ dZ,
+                                                           __bf16* __restrict__ dZ16) {
     // per-channel operands as float4 (C % 4 == 0, 16-byte aligned: launch_bn_train_backward)
     const int c4 = C >> 2;
     const int64_t total = M * c4;
@@ -274,7 +288,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
             o[j] = v * k2[j];
         }
         const int64_t b = small ? (int64_t)((uint32_t)m / (uint32_t)T_out) : m / T_out, t = m - b * T_out;
-        *(f32x4*)(dZ + (b * dz_T + t + dz_off) * C + c) = o;
+        if constexpr (F32) *(f32x4*)(dZ + (b * dz_T + t + dz_off) * C + c) = o;
+        if constexpr (H16) *(bf16x4*)(dZ16 + (b * dz_T + t + dz_off) * C + c) = to_bf16x4(o);
     }
 }
 
@@ -327,6 +342,7 @@ __global__ __launch_bounds__(256) void wgrad_f32_kernel(WgradParams p) {
     const int kk = k0 + lc;
     const int tapv = kk / p.cin, cv = kk - tapv * p.cin;
     const bool kvec = (p.cin % 4 == 0) && (kk + 3 < p.K);
+    const float* const X = (const float*)p.X;
     float4 ra[2], rb[2];
 
     auto gload = [&](int64_t m0) {
@@ -339,7 +355,7 @@ __global__ __launch_bounds__(256) void wgrad_f32_kernel(WgradParams p) {
                 b = m / p.T_out;
                 t = m - b * p.T_out;
             }
-            const float* dzr = p.dZ + (b * p.dz_T + t + p.dz_off) * (int64_t)p.ldz;
+            const float* dzr = (const float*)p.dZ + (b * p.dz_T + t + p.dz_off) * (int64_t)p.ldz;
             if (nvec) {
                 ra[i] = ld4_or_zero(dzr + n0 + lc, mv);
             } else {
@@ -350,7 +366,7 @@ __global__ __launch_bounds__(256) void wgrad_f32_kernel(WgradParams p) {
             }
             const int64_t srow = b * p.T_in + t * p.stride;
             if (kvec) {
-                rb[i] = ld4_or_zero(p.X + (srow + (int64_t)tapv * p.dil) * p.cin + cv, mv);
+                rb[i] = ld4_or_zero(X + (srow + (int64_t)tapv * p.dil) * p.cin + cv, mv);
             } else {
                 float v[4];
 #pragma unroll
@@ -359,7 +375,7 @@ __global__ __launch_bounds__(256) void wgrad_f32_kernel(WgradParams p) {
                     float x = 0.f;
                     if (mv && k < p.K) {
                         const int tap = k / p.cin, c = k - tap * p.cin;
-                        x = p.X[(srow + (int64_t)tap * p.dil) * p.cin + c];
+                        x = X[(srow + (int64_t)tap * p.dil) * p.cin + c];
                     }
                     v[j] = x;
                 }
@@ -557,8 +573,16 @@ int64_t train_reduce_part_doubles(int64_t M, int C) {
 hipError_t launch_pack_weights(const float* w, int cout, int cin, int taps, int mode, int Kp, float* out,
                                hipStream_t s) {
     const int64_t total = (int64_t)cout * cin * taps;
-    hipLaunchKernelGGL(pack_weights_kernel, dim3(grid_for(total)), dim3(256), 0, s, w, cout, cin, taps, mode, Kp,
-                       out);
+    hipLaunchKernelGGL(pack_weights_kernel<float>, dim3(grid_for(total)), dim3(256), 0, s, w, cout, cin, taps, mode,
+                       Kp, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_pack_weights_bf16(const float* w, int cout, int cin, int taps, int mode, int Kp, void* out,
+                                    hipStream_t s) {
+    const int64_t total = (int64_t)cout * cin * taps;
+    hipLaunchKernelGGL(pack_weights_kernel<__bf16>, dim3(grid_for(total)), dim3(256), 0, s, w, cout, cin, taps, mode,
+                       Kp, (__bf16*)out);
     return hipGetLastError();
 }
 
@@ -576,17 +600,24 @@ hipError_t launch_bn_train_stats(const float* Z, int64_t M, int C, double* part,
 
 hipError_t launch_bn_act_fwd(const float* Z, int64_t M, int C, const float* alpha, const float* shift, float p,
                              uint64_t seed, int layer, const float* R, int T_out, int R_T, int R_stride, int R_off,
-                             float* Y, hipStream_t s) {
+                             float* Y, void* Y16, hipStream_t s) {
     const float dscale = p > 0.f ? 1.0f / (float)(1.0 - (double)p) : 1.0f;
-    hipLaunchKernelGGL(bn_act_fwd_kernel, dim3(grid_for(M * (C / 4))), dim3(256), 0, s, Z, M, C, alpha, shift, dscale,
-                       seed, keep_threshold(p), layer, R, T_out, R_T, R_stride, R_off, Y);
+    if (Y16)
+        hipLaunchKernelGGL(bn_act_fwd_kernel<true>, dim3(grid_for(M * (C / 4))), dim3(256), 0, s, Z, M, C, alpha,
+                           shift, dscale, seed, keep_threshold(p), layer, R, T_out, R_T, R_stride, R_off, Y,
+                           (__bf16*)Y16);
+    else
+        hipLaunchKernelGGL(bn_act_fwd_kernel<false>, dim3(grid_for(M * (C / 4))), dim3(256), 0, s, Z, M, C, alpha,
+                           shift, dscale, seed, keep_threshold(p), layer, R, T_out, R_T, R_stride, R_off, Y,
+                           (__bf16*)nullptr);
     return hipGetLastError();
 }
 
 hipError_t launch_bn_train_backward(const float* dO, const float* Z, int64_t M, int C, const float* gamma,
                                     const float* alpha, const float* shift, const float* mean, const float* invstd,
                                     float p, uint64_t seed, int layer, double* part, float* coef, float* dgamma,
-                                    float* dbeta, int T_out, int dz_T, int dz_off, float* dZ, hipStream_t s) {
+                                    float* dbeta, int T_out, int dz_T, int dz_off, float* dZ, void* dZ16,
+                                    hipStream_t s) {
     const float dscale = p > 0.f ? 1.0f / (float)(1.0 - (double)p) : 1.0f;
     const uint64_t thresh = keep_threshold(p);
     BnBwdOp op{dO, Z, alpha, shift, mean, C, dscale, seed, thresh, layer};
@@ -595,8 +626,17 @@ hipError_t launch_bn_train_backward(const float* dO, const float* Z, int64_t M, 
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, s, part, nc, M, C, gamma, invstd,
                        dgamma, dbeta, coef);
-    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid_for(M * (C / 4))), dim3(256), 0, s, dO, Z, M, C, alpha, shift,
-                       mean, coef, dscale, seed, thresh, layer, T_out, dz_T, dz_off, dZ);
+    const dim3 grid(grid_for(M * (C / 4)));
+    __bf16* const d16 = (__bf16*)dZ16;
+    if (dZ && d16)
+        hipLaunchKernelGGL((bn_bwd_apply_kernel<true, true>), grid, dim3(256), 0, s, dO, Z, M, C, alpha, shift, mean,
+                           coef, dscale, seed, thresh, layer, T_out, dz_T, dz_off, dZ, d16);
+    else if (d16)
+        hipLaunchKernelGGL((bn_bwd_apply_kernel<false, true>), grid, dim3(256), 0, s, dO, Z, M, C, alpha, shift, mean,
+                           coef, dscale, seed, thresh, layer, T_out, dz_T, dz_off, dZ, d16);
+    else
+        hipLaunchKernelGGL((bn_bwd_apply_kernel<true, false>), grid, dim3(256), 0, s, dO, Z, M, C, alpha, shift, mean,
+                           coef, dscale, seed, thresh, layer, T_out, dz_T, dz_off, dZ, d16);
     return hipGetLastError();
 }
 
@@ -626,13 +666,18 @@ int wgrad_splits(int64_t M, int N, int K, int64_t max_part_floats) {
     return (int)S;
 }
 
-hipError_t launch_wgrad(const WgradParams& p0, int S, int taps, float* dW, hipStream_t s) {
+hipError_t launch_wgrad(const WgradParams& p0, int S, int taps, float* dW, hipStream_t s, bool bf16_rows) {
     WgradParams p = p0;
     const int64_t rps = (p.M + S - 1) / S;
-    p.rows_per_split = (rps + WG_R - 1) / WG_R * WG_R;
-    const int tiles = ((p.N + WG_T - 1) / WG_T) * ((p.K + WG_T - 1) / WG_T);
-    hipLaunchKernelGGL(wgrad_f32_kernel, dim3(tiles, S), dim3(256), 0, s, p);
-    hipError_t e = hipGetLastError();
+    hipError_t e;
+    if (bf16_rows) {
+        e = launch_wgrad_bf16_tiles(p, S, s);  // train_bf16.hip: same tiles and splits, 16-bit MFMA
+    } else {
+        p.rows_per_split = (rps + WG_R - 1) / WG_R * WG_R;
+        const int tiles = ((p.N + WG_T - 1) / WG_T) * ((p.K + WG_T - 1) / WG_T);
+        hipLaunchKernelGGL(wgrad_f32_kernel, dim3(tiles, S), dim3(256), 0, s, p);
+        e = hipGetLastError();
+    }
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(grid_for((int64_t)p.N * p.K)), dim3(256), 0, s, p.part, S, p.N, p.K,
                        p.cin, taps, dW);

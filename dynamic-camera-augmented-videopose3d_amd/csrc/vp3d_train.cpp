@@ -13,6 +13,15 @@
 //   wgrad     dW = dZ^T x gather(X)            wgrad_f32_kernel (train.hip)
 // BatchNorm (batch statistics), ReLU, dropout and the residual add are the
 // elementwise / per-channel passes of train.hip.
+//
+// bf16 mode (vp3d_trainer_set_compute(VP3D_DTYPE_BF16)): the three GEMMs of every BLOCK conv
+// (layers 1 .. nl-2) take bf16 operands, each rounded to nearest even from the f32 value the f32
+// step uses, with f32 accumulation: bf16 weight packs re-rounded from the parameters on every
+// call, a bf16 copy of Out[l] written by the pass that writes Out[l], dZ[l] written as bf16 by the
+// BatchNorm backward, wgrad_bf16_kernel (train_bf16.hip).  The expand conv, the shrink and every
+// element-wise / per-channel pass stay f32.  The conv GEMMs read the 16-bit rows where the layer's
+// K needs no padding (K == Kp: a 16-bit-row kernel steps through Kp); otherwise they read the
+// f32 rows and round them on load (the same rounding).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -39,6 +48,10 @@ struct TrainLayer {
     float* wf = nullptr;  // forward pack [Np][Kp]
     float* wd = nullptr;  // dgrad pack [Np_d][Kp_d]
     int Nd = 0, Kd = 0, Np_d = 0, Kp_d = 0;
+    void* wf16 = nullptr;  // bf16 mode, block convs: the same packs in bf16
+    void* wd16 = nullptr;
+    float* cap = nullptr;  // vp3d_train_capture: the gradient rows the last backward consumed
+    int64_t cap_floats = 0;
 };
 
 }  // namespace
@@ -57,8 +70,17 @@ struct vp3d_trainer {
     size_t arena_bytes = 0;
     int cap_B = 0, cap_T = 0;
     std::vector<float*> Z, Out;  // per conv layer except shrink: pre-BN and post-activation rows
+    std::vector<void*> Out16;    // bf16 mode: bf16 copy of Out[l], l <= nl-3 (the block convs' inputs)
+    bool arena_h16 = false;      // the arena holds the bf16 copies
     float* g[3] = {nullptr, nullptr, nullptr};
     float* dZ = nullptr;
+    void* dZ16 = nullptr;
+    int compute = VP3D_DTYPE_F32;      // vp3d_trainer_set_compute
+    int fwd_compute = VP3D_DTYPE_F32;  // of the latest forward
+    bool capture = false, have_bwd = false;
+    // vp3d_train_profile: event pairs around the launches of each role (kRole*)
+    bool prof = false;
+    std::vector<hipEvent_t> ev_a[4], ev_b[4];
     double* red = nullptr;
     float* coef = nullptr;
     float* wpart = nullptr;
@@ -90,6 +112,29 @@ int lin(const vp3d_trainer* t, const std::vector<int>& len, int l, int T) { retu
 
 int dz_pad(const Layer& L) { return dgrad_mode(L) == 1 ? (L.taps - 1) * L.dil : 0; }
 
+enum { kRoleFwd = 0, kRoleDgrad = 1, kRoleWgrad = 2, kRoleElem = 3 };
+
+// measurement (vp3d_train_profile): an event before / after the launches of one role
+void role_mark(vp3d_trainer* t, int role, bool end, hipStream_t s) {
+    if (!t->prof) return;
+    hipEvent_t e;
+    if (hipEventCreate(&e) != hipSuccess) return;
+    hipEventRecord(e, s);
+    (end ? t->ev_b : t->ev_a)[role].push_back(e);
+}
+
+void role_clear(vp3d_trainer* t) {
+    for (int r = 0; r < 4; ++r) {
+        for (hipEvent_t e : t->ev_a[r]) hipEventDestroy(e);
+        for (hipEvent_t e : t->ev_b[r]) hipEventDestroy(e);
+        t->ev_a[r].clear();
+        t->ev_b[r].clear();
+    }
+}
+
+// block conv: its three GEMMs take bf16 operands in bf16 mode
+bool is_block(const vp3d_trainer* t, int l) { return l >= 1 && l <= (int)t->layers.size() - 2; }
+
 int reserve(vp3d_trainer* t, int B, int T) {
     std::vector<int> len;
     if (!layer_lengths(t->cfg, t->pad, t->layers, T, len))
@@ -101,10 +146,16 @@ int reserve(vp3d_trainer* t, int B, int T) {
             return fail(VP3D_ERR_ASSERT, "strided training needs input frames = receptive field (T = " +
                                              std::to_string(T) + ")");
     }
-    if (t->arena && B <= t->cap_B && T <= t->cap_T) return VP3D_OK;
+    const bool h16 = t->compute == VP3D_DTYPE_BF16;
+    if (t->arena && B <= t->cap_B && T <= t->cap_T && t->arena_h16 == h16) return VP3D_OK;
+    if (t->arena && t->arena_h16 != h16) {  // keep the capacity across a mode change
+        B = std::max(B, t->cap_B);
+        T = std::max(T, t->cap_T);
+        layer_lengths(t->cfg, t->pad, t->layers, T, len);
+    }
     const int C = t->cfg.channels;
     size_t floats = 0;
-    std::vector<size_t> zoff, ooff;
+    std::vector<size_t> zoff, ooff, o16off;
     int64_t max_rows = 0, max_dz = 0, max_red = 0;
     for (int l = 0; l < nl; ++l) {
         const int64_t M = (int64_t)B * len[l];
@@ -115,6 +166,10 @@ int reserve(vp3d_trainer* t, int B, int T) {
             floats += (size_t)M * C;
             ooff.push_back(floats);
             floats += (size_t)M * C;
+            if (h16 && l <= nl - 3) {  // C % 8 == 0: M * C / 2 floats, 16-byte aligned
+                o16off.push_back(floats);
+                floats += (size_t)M * C / 2;
+            }
             max_dz = std::max<int64_t>(max_dz, (int64_t)B * (len[l] + 2 * dz_pad(t->layers[l])) * C);
         }
         max_red = std::max<int64_t>(max_red, train_reduce_part_doubles(M, std::max(C, t->layers[l].cout)));
@@ -123,6 +178,8 @@ int reserve(vp3d_trainer* t, int B, int T) {
     floats += 3 * (size_t)max_rows * C;
     const size_t dz_off = floats;
     floats += (size_t)max_dz;
+    const size_t dz16_off = floats;
+    if (h16) floats += (size_t)max_dz / 2;
     const size_t coef_off = floats;
     floats += 3 * (size_t)C;
     // split-row weight-gradient partials: up to kWgradPartFloats, and never less than one
@@ -143,6 +200,7 @@ int reserve(vp3d_trainer* t, int B, int T) {
     t->arena_bytes = 0;
     HIP_TRY(hipMalloc(&t->arena, bytes));
     t->arena_bytes = bytes;
+    t->arena_h16 = h16;
     t->cap_B = B;
     t->cap_T = T;
     float* f = (float*)t->arena;
@@ -152,8 +210,11 @@ int reserve(vp3d_trainer* t, int B, int T) {
         t->Z.push_back(f + zoff[i]);
         t->Out.push_back(f + ooff[i]);
     }
+    t->Out16.clear();
+    for (size_t i = 0; i < o16off.size(); ++i) t->Out16.push_back(f + o16off[i]);
     for (int i = 0; i < 3; ++i) t->g[i] = f + g_off + (size_t)i * max_rows * C;
     t->dZ = f + dz_off;
+    t->dZ16 = h16 ? (void*)(f + dz16_off) : nullptr;
     t->coef = f + coef_off;
     t->wpart = f + wpart_off;
     t->wpart_floats = wpart_floats;
@@ -241,11 +302,15 @@ int vp3d_trainer_destroy(vp3d_trainer* t) {
     for (TrainLayer& T : t->tl) {
         hipFree(T.wf);
         hipFree(T.wd);
+        hipFree(T.wf16);
+        hipFree(T.wd16);
+        hipFree(T.cap);
     }
     hipFree(t->ones);
     hipFree(t->zeros);
     hipFree(t->bn);
     hipFree(t->arena);
+    role_clear(t);
     hipSetDevice(prev);
     delete t;
     return VP3D_OK;
@@ -281,17 +346,26 @@ int vp3d_train_forward(vp3d_trainer* t, float* const* params, int n_params, cons
     std::vector<int> len;
     layer_lengths(t->cfg, t->pad, t->layers, T, len);
     t->have_fwd = false;
+    t->have_bwd = false;
+    const bool h16 = t->compute == VP3D_DTYPE_BF16;
 
+    role_mark(t, kRoleElem, false, s);
     for (int l = 0; l < nl; ++l) {
         const Layer& L = t->layers[l];
-        HIP_TRY(launch_pack_weights(params[widx(l)], L.cout, L.cin, L.taps, 0, L.Kp, t->tl[l].wf, s));
+        if (h16 && is_block(t, l))
+            HIP_TRY(launch_pack_weights_bf16(params[widx(l)], L.cout, L.cin, L.taps, 0, L.Kp, t->tl[l].wf16, s));
+        else
+            HIP_TRY(launch_pack_weights(params[widx(l)], L.cout, L.cin, L.taps, 0, L.Kp, t->tl[l].wf, s));
     }
+    role_mark(t, kRoleElem, true, s);
     for (int l = 0; l < nl; ++l) {
         const Layer& L = t->layers[l];
         const bool last = l == nl - 1;
+        const bool b16 = h16 && is_block(t, l);
+        const bool rows16 = b16 && L.Kp == L.K;  // else f32 rows rounded on load
         ConvGemmParams p = gemm_base(t);
-        p.A = l == 0 ? (const void*)x : (const void*)t->Out[l - 1];
-        p.W = t->tl[l].wf;
+        p.A = l == 0 ? (const void*)x : rows16 ? (const void*)t->Out16[l - 1] : (const void*)t->Out[l - 1];
+        p.W = b16 ? t->tl[l].wf16 : (const void*)t->tl[l].wf;
         p.M = B * len[l];
         p.N = L.cout;
         p.K = L.K;
@@ -309,8 +383,11 @@ int vp3d_train_forward(vp3d_trainer* t, float* const* params, int n_params, cons
         } else {
             p.Y = t->Z[l];
         }
-        HIP_TRY(launch_conv_gemm(p, Act::F32, Act::F32, Act::F32, s));
+        role_mark(t, kRoleFwd, false, s);
+        HIP_TRY(launch_conv_gemm(p, rows16 ? Act::BF16 : Act::F32, Act::F32, b16 ? Act::BF16 : Act::F32, s));
+        role_mark(t, kRoleFwd, true, s);
         if (last) break;
+        role_mark(t, kRoleElem, false, s);
         const int64_t M = (int64_t)B * len[l];
         float* const* bp = params + widx(l) + 1;  // weight, bias, running_mean, running_var
         HIP_TRY(launch_bn_train_stats(t->Z[l], M, C, t->red, bp[0], bp[1], t->cfg.bn_eps, momentum, bp[2], bp[3],
@@ -322,9 +399,12 @@ int vp3d_train_forward(vp3d_trainer* t, float* const* params, int n_params, cons
             R_T = len[l - 2];
         }
         HIP_TRY(launch_bn_act_fwd(t->Z[l], M, C, bn_arr(t, l, 2), bn_arr(t, l, 3), dropout_p, seed, l, R, len[l], R_T,
-                                  L.res_stride, L.res_off, t->Out[l], s));
+                                  L.res_stride, L.res_off, t->Out[l], (h16 && l <= nl - 3) ? t->Out16[l] : nullptr,
+                                  s));
+        role_mark(t, kRoleElem, true, s);
     }
     t->have_fwd = true;
+    t->fwd_compute = t->compute;
     t->B = B;
     t->T = T;
     t->len = len;
@@ -340,6 +420,9 @@ int vp3d_train_backward(vp3d_trainer* t, float* const* params, int n_params, con
     if (!t->have_fwd) return fail(VP3D_ERR_STATE, "vp3d_train_backward without a forward");
     if (!params || !dy || !grads) return fail(VP3D_ERR_ARG, "NULL argument");
     if (n_params != vp3d_weight_count(&t->cfg)) return fail(VP3D_ERR_ARG, "parameter count mismatch");
+    if (t->fwd_compute != t->compute)
+        return fail(VP3D_ERR_STATE, "the compute dtype changed between the forward and this backward");
+    const bool h16 = t->compute == VP3D_DTYPE_BF16;
     const int nl = (int)t->layers.size();
     for (int l = 0; l < nl; ++l) {
         const bool last = l == nl - 1;
@@ -355,19 +438,41 @@ int vp3d_train_backward(vp3d_trainer* t, float* const* params, int n_params, con
     const int B = t->B, T = t->T;
     const std::vector<int>& len = t->len;
 
+    role_mark(t, kRoleElem, false, s);
     for (int l = 1; l < nl; ++l) {
         const Layer& L = t->layers[l];
         const TrainLayer& TL = t->tl[l];
-        HIP_TRY(launch_pack_weights(params[widx(l)], L.cout, L.cin, L.taps, dgrad_mode(L), TL.Kp_d, TL.wd, s));
+        if (h16 && is_block(t, l))
+            HIP_TRY(launch_pack_weights_bf16(params[widx(l)], L.cout, L.cin, L.taps, dgrad_mode(L), TL.Kp_d, TL.wd16,
+                                             s));
+        else
+            HIP_TRY(launch_pack_weights(params[widx(l)], L.cout, L.cin, L.taps, dgrad_mode(L), TL.Kp_d, TL.wd, s));
     }
-    auto wgrad = [&](int l, const float* dz, int ldz, int dz_T, int dz_off, float* dW) -> int {
+    role_mark(t, kRoleElem, true, s);
+    // test hook: keep the gradient rows layer l's dgrad / wgrad consume (dense rows, f32)
+    auto capture = [&](int l, const void* rows, bool rows_bf16, int cout, int src_T, int src_off) -> int {
+        if (!t->capture) return VP3D_OK;
+        TrainLayer& TL = t->tl[l];
+        const int64_t n = (int64_t)B * len[l] * cout;
+        if (TL.cap_floats < n) {
+            HIP_TRY(hipFree(TL.cap));
+            TL.cap = nullptr;
+            TL.cap_floats = 0;
+            HIP_TRY(hipMalloc(&TL.cap, (size_t)n * sizeof(float)));
+            TL.cap_floats = n;
+        }
+        HIP_TRY(launch_rows_to_f32(rows, rows_bf16, (int64_t)B * len[l], cout, len[l], src_T, src_off, TL.cap, s));
+        return VP3D_OK;
+    };
+    // dz: f32 rows, or (b16) the bf16 rows of a block conv against the bf16 copy of its input
+    auto wgrad = [&](int l, const void* dz, bool b16, int ldz, int dz_T, int dz_off, float* dW) -> int {
         const Layer& L = t->layers[l];
         WgradParams w{};
         w.dZ = dz;
         w.ldz = ldz;
         w.dz_T = dz_T;
         w.dz_off = dz_off;
-        w.X = l == 0 ? t->x : t->Out[l - 1];
+        w.X = l == 0 ? (const void*)t->x : b16 ? (const void*)t->Out16[l - 1] : (const void*)t->Out[l - 1];
         w.cin = L.cin;
         w.T_in = lin(t, len, l, T);
         w.stride = L.stride;
@@ -380,16 +485,19 @@ int vp3d_train_backward(vp3d_trainer* t, float* const* params, int n_params, con
         if ((int64_t)w.N * w.K > t->wpart_floats)
             return fail(VP3D_ERR_STATE, "weight-gradient partial buffer smaller than one N x K split");
         const int S = wgrad_splits(w.M, w.N, w.K, t->wpart_floats);
-        HIP_TRY(launch_wgrad(w, S, L.taps, dW, s));
+        role_mark(t, kRoleWgrad, false, s);
+        HIP_TRY(launch_wgrad(w, S, L.taps, dW, s, b16));
+        role_mark(t, kRoleWgrad, true, s);
         return VP3D_OK;
     };
     // dgrad of layer l: gradient wrt its input rows (B * lin(l) rows of cin) into `out`
-    auto dgrad = [&](int l, const float* dz, int dz_T, float* out) -> int {
+    // a_type: the element type of `dz`; b16: bf16 operands (the bf16 pack)
+    auto dgrad = [&](int l, const void* dz, Act a_type, bool b16, int dz_T, float* out) -> int {
         const Layer& L = t->layers[l];
         const TrainLayer& TL = t->tl[l];
         ConvGemmParams p = gemm_base(t);
         p.A = dz;
-        p.W = TL.wd;
+        p.W = b16 ? TL.wd16 : (const void*)TL.wd;
         p.N = TL.Nd;
         p.K = TL.Kd;
         p.Kp = TL.Kp_d;
@@ -411,7 +519,9 @@ int vp3d_train_backward(vp3d_trainer* t, float* const* params, int n_params, con
             p.dil = 1;
             p.Ktap = L.cout;
         }
-        HIP_TRY(launch_conv_gemm(p, Act::F32, Act::F32, Act::F32, s));
+        role_mark(t, kRoleDgrad, false, s);
+        HIP_TRY(launch_conv_gemm(p, a_type, Act::F32, b16 ? Act::BF16 : Act::F32, s));
+        role_mark(t, kRoleDgrad, true, s);
         return VP3D_OK;
     };
 
@@ -419,11 +529,15 @@ int vp3d_train_backward(vp3d_trainer* t, float* const* params, int n_params, con
     const int ls = nl - 1;
     const Layer& SL = t->layers[ls];
     const int64_t Ms = (int64_t)B * len[ls];
+    role_mark(t, kRoleElem, false, s);
     HIP_TRY(launch_colsum(dy, Ms, SL.cout, SL.cout, t->red, grads[widx(ls) + 1], s));
-    rc = wgrad(ls, dy, SL.cout, len[ls], 0, grads[widx(ls)]);
+    role_mark(t, kRoleElem, true, s);
+    rc = capture(ls, dy, false, SL.cout, len[ls], 0);
+    if (rc) return rc;
+    rc = wgrad(ls, dy, false, SL.cout, len[ls], 0, grads[widx(ls)]);
     if (rc) return rc;
     int cur = 0;  // g[cur] = gradient wrt Out[l]
-    rc = dgrad(ls, dy, len[ls], t->g[cur]);
+    rc = dgrad(ls, dy, Act::F32, false, len[ls], t->g[cur]);
     if (rc) return rc;
     int block_out = -1;  // buffer holding the gradient of the current block's output
     for (int l = nl - 2; l >= 0; --l) {
@@ -431,29 +545,130 @@ int vp3d_train_backward(vp3d_trainer* t, float* const* params, int n_params, con
         const int64_t M = (int64_t)B * len[l];
         const int P = l > 0 ? dz_pad(L) : 0;
         const int dz_T = len[l] + 2 * P;
-        if (P > 0) HIP_TRY(hipMemsetAsync(t->dZ, 0, (size_t)B * dz_T * C * sizeof(float), s));
+        // bf16 mode, block conv: dZ as bf16 rows (the zero padding included); f32 rows as well only
+        // where the dgrad GEMM reads them (a K that needs padding: rounded on load)
+        const bool b16 = h16 && is_block(t, l);
+        const bool rows16 = b16 && t->tl[l].Kp_d == t->tl[l].Kd;
+        const bool need32 = !b16 || !rows16;
+        role_mark(t, kRoleElem, false, s);
+        if (P > 0 && need32) HIP_TRY(hipMemsetAsync(t->dZ, 0, (size_t)B * dz_T * C * sizeof(float), s));
+        if (P > 0 && b16) HIP_TRY(hipMemsetAsync(t->dZ16, 0, (size_t)B * dz_T * C * 2, s));
         HIP_TRY(launch_bn_train_backward(t->g[cur], t->Z[l], M, C, params[widx(l) + 1], bn_arr(t, l, 2),
                                          bn_arr(t, l, 3), bn_arr(t, l, 0), bn_arr(t, l, 1), t->p, t->seed, l, t->red,
-                                         t->coef, grads[widx(l) + 1], grads[widx(l) + 2], len[l], dz_T, P, t->dZ,
-                                         s));
-        rc = wgrad(l, t->dZ, C, dz_T, P, grads[widx(l)]);
+                                         t->coef, grads[widx(l) + 1], grads[widx(l) + 2], len[l], dz_T, P,
+                                         need32 ? t->dZ : nullptr, b16 ? t->dZ16 : nullptr, s));
+        role_mark(t, kRoleElem, true, s);
+        rc = capture(l, b16 ? t->dZ16 : (const void*)t->dZ, b16, C, dz_T, P);
+        if (rc) return rc;
+        rc = wgrad(l, b16 ? t->dZ16 : (const void*)t->dZ, b16, C, dz_T, P, grads[widx(l)]);
         if (rc) return rc;
         if (l == 0) break;
         int nxt = 0;
         while (nxt == cur || nxt == block_out) ++nxt;
-        rc = dgrad(l, t->dZ, dz_T, t->g[nxt]);
+        rc = dgrad(l, rows16 ? t->dZ16 : (const void*)t->dZ, rows16 ? Act::BF16 : Act::F32, b16, dz_T, t->g[nxt]);
         if (rc) return rc;
         if (L.residual) {
             block_out = cur;  // keep dOut of the block until the k-conv's dgrad is done
         } else if (block_out >= 0) {
             // k-conv of a block: its dgrad is the block input's gradient; add the residual path
             const Layer& PW = t->layers[l + 1];
+            role_mark(t, kRoleElem, false, s);
             HIP_TRY(launch_res_grad_add(t->g[nxt], t->g[block_out], (int64_t)B * len[l + 1], C, len[l + 1],
                                         lin(t, len, l, T), PW.res_stride, PW.res_off, s));
+            role_mark(t, kRoleElem, true, s);
             block_out = -1;
         }
         cur = nxt;
     }
+    t->have_bwd = true;
+    return VP3D_OK;
+}
+
+int vp3d_trainer_set_compute(vp3d_trainer* t, int dtype) {
+    if (!t) return fail(VP3D_ERR_ARG, "trainer is NULL");
+    if (dtype != VP3D_DTYPE_F32 && dtype != VP3D_DTYPE_BF16)
+        return fail(VP3D_ERR_ARG, "training computes in VP3D_DTYPE_F32 or VP3D_DTYPE_BF16 (fp16 and f16x3 would "
+                                  "need loss scaling)");
+    if (dtype == VP3D_DTYPE_BF16) {
+        if (t->cfg.channels % 8 != 0)
+            return fail(VP3D_ERR_ARG, "bf16 training needs channels to be a multiple of 8 (the 16-bit rows are "
+                                      "read 8 elements at a time)");
+        int rc = check_device(t);
+        if (rc) return rc;
+        const int nl = (int)t->layers.size();
+        for (int l = 1; l <= nl - 2; ++l) {
+            const Layer& L = t->layers[l];
+            TrainLayer& T = t->tl[l];
+            if (!T.wf16) {
+                if (hipMalloc(&T.wf16, (size_t)L.Np * L.Kp * 2) != hipSuccess) return fail(VP3D_ERR_OOM, "bf16 weight pack");
+                HIP_TRY(hipMemset(T.wf16, 0, (size_t)L.Np * L.Kp * 2));
+            }
+            if (!T.wd16) {
+                if (hipMalloc(&T.wd16, (size_t)T.Np_d * T.Kp_d * 2) != hipSuccess)
+                    return fail(VP3D_ERR_OOM, "bf16 dgrad weight pack");
+                HIP_TRY(hipMemset(T.wd16, 0, (size_t)T.Np_d * T.Kp_d * 2));
+            }
+        }
+    }
+    t->compute = dtype;
+    return VP3D_OK;
+}
+
+int vp3d_trainer_compute(const vp3d_trainer* t) { return t ? t->compute : -1; }
+
+int vp3d_train_profile(vp3d_trainer* t, int on, double* ms) {
+    if (!t) return fail(VP3D_ERR_ARG, "trainer is NULL");
+    int rc = check_device(t);
+    if (rc) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    if (ms) {
+        for (int r = 0; r < 4; ++r) {
+            ms[r] = 0.0;
+            const size_t n = std::min(t->ev_a[r].size(), t->ev_b[r].size());
+            for (size_t i = 0; i < n; ++i) {
+                float v = 0.f;
+                if (hipEventElapsedTime(&v, t->ev_a[r][i], t->ev_b[r][i]) == hipSuccess) ms[r] += v;
+            }
+        }
+    }
+    role_clear(t);
+    t->prof = on != 0;
+    return VP3D_OK;
+}
+
+int vp3d_train_capture(vp3d_trainer* t, int on) {
+    if (!t) return fail(VP3D_ERR_ARG, "trainer is NULL");
+    t->capture = on != 0;
+    if (!on) t->have_bwd = false;
+    return VP3D_OK;
+}
+
+int vp3d_train_read(vp3d_trainer* t, int layer, int which, float* out, int64_t n, void* stream) {
+    if (!t || !out) return fail(VP3D_ERR_ARG, "NULL argument");
+    const int nl = (int)t->layers.size();
+    if (layer < 0 || layer >= nl) return fail(VP3D_ERR_ARG, "layer out of range");
+    if (which != 0 && which != 1) return fail(VP3D_ERR_ARG, "which must be 0 (activation rows) or 1 (gradient rows)");
+    if (!t->have_fwd) return fail(VP3D_ERR_STATE, "no forward yet");
+    int rc = check_device(t);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const Layer& L = t->layers[layer];
+    if (which == 0) {
+        const int Tin = lin(t, t->len, layer, t->T);
+        const int64_t rows = (int64_t)t->B * Tin;
+        if (n != rows * L.cin) return fail(VP3D_ERR_ARG, "n must be rows * cin = " + std::to_string(rows * L.cin));
+        const bool b16 = t->fwd_compute == VP3D_DTYPE_BF16 && is_block(t, layer);
+        const void* src = layer == 0 ? (const void*)t->x
+                          : b16      ? (const void*)t->Out16[layer - 1]
+                                     : (const void*)t->Out[layer - 1];
+        HIP_TRY(launch_rows_to_f32(src, b16, rows, L.cin, Tin, Tin, 0, out, s));
+        return VP3D_OK;
+    }
+    if (!t->capture || !t->have_bwd || !t->tl[layer].cap)
+        return fail(VP3D_ERR_STATE, "gradient rows need vp3d_train_capture(t, 1) before the backward");
+    const int64_t want = (int64_t)t->B * t->len[layer] * L.cout;
+    if (n != want) return fail(VP3D_ERR_ARG, "n must be rows * cout = " + std::to_string(want));
+    HIP_TRY(hipMemcpyAsync(out, t->tl[layer].cap, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, s));
     return VP3D_OK;
 }
 

@@ -398,6 +398,8 @@ def train_main(args, data):
     print("Test Subjects: ", ", ".join(subjects_test))
     j2, j3 = joint_counts(data)
     model_pos_train = build_model(args, j2, J_out=j3).cuda()
+    # --train-dtype: the training step only; the per-epoch evaluation model keeps --compute-dtype
+    model_pos_train.set_train_dtype(getattr(args, "train_dtype", "fp32"))
     model_pos = build_model(args, j2, announce=False, J_out=j3).cuda()
     pad = (model_pos.receptive_field() - 1) // 2
     causal_shift = pad if args.causal else 0

@@ -63,6 +63,8 @@ EXPORTS = [
     "vp3d_lstream_reset", "vp3d_lstream_counts", "vp3d_lstream_graph_capture", "vp3d_lstream_graph_launch",
     "vp3d_lstream_destroy",
     "vp3d_trainer_create", "vp3d_trainer_destroy", "vp3d_train_forward", "vp3d_train_backward",
+    "vp3d_trainer_set_compute", "vp3d_trainer_compute", "vp3d_train_capture", "vp3d_train_read",
+    "vp3d_train_profile",
     "vp3d_train_dropout_mask", "vp3d_train_relu_mask", "vp3d_train_layer_rows", "vp3d_train_reduce_doubles", "vp3d_adam_step", "vp3d_mpjpe_backward",
     "vp3d_seq_weight_count", "vp3d_seq_create", "vp3d_seq_destroy", "vp3d_seq_forward",
     "vp3d_seq_sliding_window",
@@ -219,6 +221,11 @@ _SIGNATURES = {
     "vp3d_train_dropout_mask": (_int, [_vp, _int, _i64, _vp, _vp]),
     "vp3d_train_relu_mask": (_int, [_vp, _int, _i64, _vp, _vp]),
     "vp3d_train_layer_rows": (_i64, [_vp, _int]),
+    "vp3d_trainer_set_compute": (_int, [_vp, _int]),
+    "vp3d_trainer_compute": (_int, [_vp]),
+    "vp3d_train_capture": (_int, [_vp, _int]),
+    "vp3d_train_profile": (_int, [_vp, _int, ctypes.POINTER(ctypes.c_double)]),
+    "vp3d_train_read": (_int, [_vp, _int, _int, _vp, _i64, _vp]),
     "vp3d_train_reduce_doubles": (_i64, [_i64, _int, _int]),
     "vp3d_adam_step": (_int, [_int, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp),
                               ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_i64),

@@ -8,6 +8,8 @@ The reference trains `TemporalModel` in train mode inside run.py's loop
 * `NativeTrainer` owns a ``vp3d_trainer`` (include/vp3d.h): the f32 train-mode
   forward and the backward of every layer run in libvp3d.so; the parameters stay in
   the module's own tensors and are passed by device pointer on every call.
+  `set_compute('bf16')` switches the block convolutions' GEMMs to bf16 operands with f32
+  accumulation (mixed precision; everything else stays f32).
 * `TrainStep` is the autograd node the drop-in `TemporalModelBase.forward` uses in
   train mode, so a reference training loop (`loss.backward()`, any torch optimiser)
   runs unchanged.
@@ -44,6 +46,7 @@ class NativeTrainer:
         self.device = torch.device(device)
         self.num_joints_out = num_joints_out
         self.generation = 0
+        self._B = self._T = -1
         self._h = ctypes.c_void_p()
         with torch.cuda.device(self.device):
             N.check(self._lib.vp3d_trainer_create(ctypes.byref(self.cfg), ctypes.byref(self._h)),
@@ -57,6 +60,7 @@ class NativeTrainer:
         updated in place).  Returns y (B, T_out, J_out, 3)."""
         assert len(params) == self.n_params, (len(params), self.n_params)
         B, T = int(x.shape[0]), int(x.shape[1])
+        self._B, self._T = B, T
         y = torch.empty((B, T_out, self.num_joints_out, 3), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
             N.check(self._lib.vp3d_train_forward(self._h, _ptrs(params), len(params), x.data_ptr(), B, T,
@@ -78,6 +82,62 @@ class NativeTrainer:
                                                   _ptrs(grads), N.stream_ptr(self.device)),
                     "vp3d_train_backward")
         return grads
+
+    #: training compute dtypes (vp3d_trainer_set_compute); fp16 / f16x3 would need loss scaling
+    TRAIN_DTYPES = {"fp32": N.DTYPE_F32, "bf16": N.DTYPE_BF16}
+
+    def set_compute(self, dtype: str) -> None:
+        """'fp32' (default: every GEMM on the exact-f32 MFMA) or 'bf16' (the block convolutions'
+        forward, data-gradient and weight-gradient GEMMs on bf16 operands, f32 accumulation;
+        everything else f32).  Holds from the next forward."""
+        if dtype not in self.TRAIN_DTYPES:
+            raise ValueError(f"unknown training dtype {dtype!r} (fp32 or bf16)")
+        with torch.cuda.device(self.device):
+            N.check(self._lib.vp3d_trainer_set_compute(self._h, self.TRAIN_DTYPES[dtype]),
+                    "vp3d_trainer_set_compute")
+
+    @property
+    def compute(self) -> str:
+        code = int(self._lib.vp3d_trainer_compute(self._h))
+        return {v: k for k, v in self.TRAIN_DTYPES.items()}[code]
+
+    def capture(self, on: bool) -> None:
+        """Test hook: while on, every backward keeps the gradient rows each conv consumed
+        (read(layer, 1)); extra memory, small shapes only."""
+        N.check(self._lib.vp3d_train_capture(self._h, 1 if on else 0), "vp3d_train_capture")
+
+    def read(self, layer: int, which: int) -> torch.Tensor:
+        """Test hook: the rows conv `layer` consumed in the latest forward (which = 0: its
+        activation operand, B * input frames rows of cin) or backward (which = 1: the gradient
+        rows of its dgrad / wgrad, B * output frames rows of cout; needs capture(True)), as f32
+        (in bf16 mode the bf16 operands of a block conv, widened)."""
+        n_layers = 2 * self.cfg.n_widths
+        if not 0 <= layer < n_layers:
+            raise RuntimeError(f"layer {layer} out of range")
+        c, jf = self.cfg.channels, self.cfg.num_joints_in * self.cfg.in_features
+        if which == 0:
+            rows = self._B * self._T if layer == 0 else self.layer_rows(layer - 1)
+            width = jf if layer == 0 else c
+        else:
+            rows = self.layer_rows(layer)
+            width = self.num_joints_out * 3 if layer == n_layers - 1 else c
+        if rows < 0:
+            raise RuntimeError("no train-mode forward yet")
+        out = torch.empty((rows, width), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            N.check(self._lib.vp3d_train_read(self._h, layer, which, out.data_ptr(), out.numel(),
+                                              N.stream_ptr(self.device)), "vp3d_train_read")
+        return out
+
+    ROLES = ("forward_gemm", "dgrad_gemm", "wgrad", "elementwise")
+
+    def profile(self, on: bool) -> dict:
+        """Measurement: the device milliseconds per role (ROLES) of the steps run since profiling
+        was switched on, then switch it on or off (vp3d_train_profile; synchronises)."""
+        ms = (ctypes.c_double * 4)()
+        with torch.cuda.device(self.device):
+            N.check(self._lib.vp3d_train_profile(self._h, 1 if on else 0, ms), "vp3d_train_profile")
+        return dict(zip(self.ROLES, [float(v) for v in ms]))
 
     def layer_rows(self, layer: int) -> int:
         return int(self._lib.vp3d_train_layer_rows(self._h, layer))

@@ -477,6 +477,49 @@ int vp3d_train_dropout_mask(vp3d_trainer* t, int layer, int64_t n_elems, uint8_t
  * parity tests feed this mask (with the dropout mask) to the oracle. */
 int vp3d_train_relu_mask(vp3d_trainer* t, int layer, int64_t n_elems, uint8_t* out, void* stream);
 
+/* Mixed-precision training.  dtype: VP3D_DTYPE_F32 (the default: every GEMM on the exact-f32
+ * MFMA) or VP3D_DTYPE_BF16; anything else is VP3D_ERR_ARG (fp16 / f16x3 training would need
+ * loss scaling: the gradients of a mean-over-batch MPJPE lie far below f16's range).  In bf16
+ * mode the three GEMMs of every BLOCK convolution (conv layers 1 .. n-2: each block's k-conv
+ * and its 1x1) take bf16 operands, each rounded to nearest even from the f32 value the f32
+ * step uses, and accumulate in f32:
+ *   forward          Z[l]  = conv(bf16(Out[l-1]), bf16(W[l]))
+ *   data gradient    dX    = conv^T(bf16(dZ[l]), bf16(W[l]))
+ *   weight gradient  dW[l] = bf16(dZ[l])^T x gather(bf16(Out[l-1]))
+ * The expand conv (2D coordinates in) and the shrink (metre-scale poses out) keep the f32 path
+ * in every role; BatchNorm statistics, the BN / ReLU / dropout / residual passes, the gradients
+ * handed back, the parameters and Adam stay f32.  The weights are re-rounded from the f32
+ * parameters on every forward and backward call.  channels % 8 != 0 is VP3D_ERR_ARG in bf16
+ * mode (the 16-bit rows are read 8 elements at a time).  The setting holds from the next
+ * forward; a backward whose forward ran under another setting is VP3D_ERR_STATE. */
+int vp3d_trainer_set_compute(vp3d_trainer* t, int dtype);
+/* The setting of vp3d_trainer_set_compute (-1 for NULL). */
+int vp3d_trainer_compute(const vp3d_trainer* t);
+
+/* Test hooks for the parity tests of the bf16 mode (small shapes only: extra memory).
+ * vp3d_train_capture(t, on): while on, every backward keeps, per conv layer, a dense f32 copy
+ * of the gradient rows that layer's dgrad and wgrad consumed (what `which` = 1 returns).
+ * vp3d_train_read(t, layer, which, out, n, stream), for the latest forward / backward:
+ *   which = 0  the rows conv `layer` consumed as its activation operand: B * (input frames of
+ *              the layer) rows of cin values (layer 0: x itself, read through the forward's
+ *              pointer, which the caller must still hold)
+ *   which = 1  the gradient rows its dgrad and wgrad consumed: B * (output frames) rows of
+ *              cout values, without the dgrad's zero padding (the shrink: dy); needs capture
+ * In bf16 mode the rows of a block conv are the bf16 operands widened to f32 (exact); otherwise
+ * the f32 rows.  out: device f32, n = rows * width.  VP3D_ERR_STATE without a forward, or
+ * (which = 1) without capture on during the latest backward; VP3D_ERR_ARG for a wrong n,
+ * layer or which. */
+int vp3d_train_capture(vp3d_trainer* t, int on);
+int vp3d_train_read(vp3d_trainer* t, int layer, int which, float* out, int64_t n, void* stream);
+
+/* Measurement (tools/bench_train_dtype.py).  Synchronises the device; if `ms` is not NULL it
+ * receives the device time, in milliseconds and summed since the previous call, of four roles
+ * of the forwards and backwards run with profiling on: [0] forward conv GEMMs, [1] data-gradient
+ * GEMMs, [2] weight gradients (tiles + split reduce), [3] the element-wise / per-channel passes
+ * (weight packs, BatchNorm, ReLU / dropout / residual, column sums).  Then profiling is switched
+ * on or off.  While on, every launch group is bracketed by two events (a little slower). */
+int vp3d_train_profile(vp3d_trainer* t, int on, double* ms);
+
 /* Row count (B * frames) of conv layer `layer`'s output in the latest forward, or -1. */
 int64_t vp3d_train_layer_rows(const vp3d_trainer* t, int layer);
 
