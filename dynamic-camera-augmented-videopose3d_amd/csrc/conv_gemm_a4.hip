@@ -168,6 +168,9 @@ __global__ __launch_bounds__(256, 1) void conv_gemm_a4(ConvGemmParams p_arg) {
     constexpr int NJ = TN / 32;    // channel blocks of 16 per wave (two wave columns)
     constexpr int WP = TN / 32;    // W pieces per wave and K-tile (TN rows x 128 B, 4 waves)
     constexpr int NB = NJ < 4 ? NJ : 4;  // blocks of a 64-channel epilogue half
+    // a gated launch (the edge segments of a trimmed frame table, ConvGemmParams::gate) runs only
+    // in the forward whose bases kernel opened it: one uniform load and compare, then as ungated
+    if (p_arg.gate != nullptr && *p_arg.gate != p_arg.gate_serial) return;
     // the accumulator file is this kernel's own from here on (see the header)
     asm volatile("" ::: A4_ALL_AGPRS);
     // a copy whose fields go through an empty asm every tile (below): values derived from them
@@ -1290,6 +1293,9 @@ static int a4_cus() {
     }();
     return ncu;
 }
+
+int conv_gemm_a4_round_tiles() { return a4_cus(); }
+int64_t conv_gemm_a4_tiles(int64_t rows, int N) { return (rows + GM - 1) / GM * (N / GN); }
 
 // Split-K plan of a launch's partial last round: L = the tiles past the last whole round of the
 // chip's CUs, each split into S = CUs / L units (<= 4) of an equal whole number (even, >= 4) of

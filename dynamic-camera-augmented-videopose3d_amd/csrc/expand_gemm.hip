@@ -102,6 +102,9 @@ __global__ __launch_bounds__(256, (X3 && RING == 1) ? 3 : 2) void expand_gemm_h1
     __shared__ __attribute__((aligned(16))) char smem[RING * kChunk +
                                                       (X3 ? (kSsLds ? 2 * kExpMaxN * 4 : 0) : kExpWaves * kRowsW * 128)];
 
+    // a gated launch (a trimmed table's edge fill, ConvGemmParams::gate): only when opened
+    if constexpr (X3)
+        if (p.gate != nullptr && *p.gate != p.gate_serial) return;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wid = tid >> 6;
@@ -717,6 +720,8 @@ __global__ __launch_bounds__(64 * kWsWaves) void expand_gemm_x3_ws(ConvGemmParam
     const int n0 = (blockIdx.x - stripe * nh) * kWsN + wid * 64;
     const int ngroups = (p.M + kWsRows - 1) / kWsRows;
     if (stripe >= ngroups) return;  // (the whole workgroup)
+    // a gated launch (a trimmed table's edge fill, ConvGemmParams::gate): only when opened
+    if (p.gate != nullptr && *p.gate != p.gate_serial) return;
 
     // this wave's weights: row n0 + 16 j + (l & 15), k-chunk l >> 4 of each k-slab's hi and lo
     // halves -- the fragments the chunked kernel reads from its LDS image

@@ -14,8 +14,18 @@
 //                       pool is a fault.  With frame tables (vp3d_capi.cpp, plan_frame_tables:
 //                       blocks 1 .. d computed once per table row too, level l with its own
 //                       pitch) the bases are those of the deepest level: the same clamp, the
-//                       pitch of that level in place of T_tab, read at j * step_{d+1}
-//   gather_table_rows   the windows' rows copied out of the table into the contiguous
+//                       pitch of that level in place of T_tab, read at j * step_{d+1}.
+//                       Trimmed layout (WindowRegions, vp3d_capi.cpp plan_table_layout): the main
+//                       region holds the starts 0 .. max_len - 1 only (a start past a short
+//                       sequence's end but below max_len clamps to len - 1 + lead and is served by
+//                       it); a clamped start below 0 or from max_len on gets its base in the
+//                       sequence's low / high edge segment, and the kernel raises the gate word
+//                       to this forward's serial so that the edge launches (which return at
+//                       entry otherwise, leaving stale rows nothing reads) fill those segments.
+//                       Either layout: the two host-mapped hint words take the serial of the
+//                       last launch and of the last launch that met such a start.  Launched at
+//                       the front of the forward: the bases' place is written by no table launch
+//   gather_table_rows  the windows' rows copied out of the table into the contiguous
 //                       (B, T_out) layout the expand conv itself writes (kernel forms without
 //                       indirect windows; the bit-identity reference of the tests)
 #include "kernels.h"
@@ -27,9 +37,11 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 __global__ __launch_bounds__(256) void window_bases_kernel(const int32_t* __restrict__ pairs,
                                                            const int32_t* __restrict__ seq_len, int B, int n_seq,
-                                                           int T_tab, int lo, int lead, int32_t* __restrict__ base,
-                                                           unsigned* fault) {
+                                                           WindowRegions wr, int lo, int lead,
+                                                           int32_t* __restrict__ base, unsigned* fault) {
     const int b = blockIdx.x * 256 + threadIdx.x;
+    // (host-mapped: the host reads it without waiting, to choose the next forward's layout)
+    if (b == 0 && wr.hint) __hip_atomic_store(wr.hint, wr.serial, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     if (b >= B) return;
     const int2 pr = *(const int2*)(pairs + 2 * b);
     // a sequence outside the pool has no table rows: fault, and a base inside the table so that
@@ -37,8 +49,21 @@ __global__ __launch_bounds__(256) void window_bases_kernel(const int32_t* __rest
     const bool ok = pr.x >= 0 && pr.x < n_seq;
     const int hi = seq_len[ok ? pr.x : 0] - 1 + lead;  // (>= lo: lo <= 0, len >= 1, lead >= 0)
     const int st = pr.y < lo ? lo : (pr.y > hi ? hi : pr.y);
-    base[b] = ok ? pr.x * T_tab + (st - lo) : 0;
+    // the region: the main rows, or in the trimmed layout the sequence's low / high edge segment
+    const bool low = st < 0, high = st >= wr.max_len;
+    int row = pr.x * wr.pitch + (st - wr.main_lo);
+    if (wr.epitch > 0 && low) row = wr.edge_row0 + 2 * pr.x * wr.epitch + (st - lo);
+    if (wr.epitch > 0 && high) row = wr.edge_row0 + (2 * pr.x + 1) * wr.epitch + (st - wr.max_len);
+    base[b] = ok ? row : 0;
     if (!ok && fault) __hip_atomic_fetch_or(fault, kFaultWindowStart, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    // a start outside the main region's: opens this forward's edge launches (the serial only
+    // grows, so nothing is zeroed per forward), one lane per wave
+    const bool edge = ok && (low || high);
+    const unsigned long long em = __ballot(edge);
+    if (edge && (threadIdx.x & 63) == __ffsll((long long)em) - 1) {
+        if (wr.gate) __hip_atomic_fetch_max(wr.gate, wr.serial, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (wr.hint) __hip_atomic_store(wr.hint + 1, wr.serial, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
 }
 
 // out row (b, t) = table row base[b] + t * s0; rows of `row16` 16-byte words, one word per lane,
@@ -64,11 +89,11 @@ __global__ __launch_bounds__(256) void gather_table_rows_kernel(const u32x4* __r
 
 }  // namespace
 
-hipError_t launch_window_bases(const int32_t* pairs, const int32_t* seq_len, int B, int n_seq, int T_tab, int lo,
-                               int lead, int32_t* base, unsigned* fault, hipStream_t s) {
-    if (lo > 0 || lead < 0) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(window_bases_kernel, dim3((B + 255) / 256), dim3(256), 0, s, pairs, seq_len, B, n_seq, T_tab,
-                       lo, lead, base, fault);
+hipError_t launch_window_bases(const int32_t* pairs, const int32_t* seq_len, int B, int n_seq, const WindowRegions& wr,
+                               int lo, int lead, int32_t* base, unsigned* fault, hipStream_t s) {
+    if (lo > 0 || lead < 0 || wr.main_lo > 0 || wr.main_lo < lo || wr.epitch < 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(window_bases_kernel, dim3((B + 255) / 256), dim3(256), 0, s, pairs, seq_len, B, n_seq, wr, lo,
+                       lead, base, fault);
     return hipGetLastError();
 }
 

@@ -125,8 +125,9 @@ struct vp3d_handle {
     // expand table of an f16x3 vp3d_forward_windows_pool (forward_impl's table path,
     // expand_table.hip): one allocation of slots [window bases: B int32, padded | table: n_seq *
     // T_tab split rows] -- one slot, or three rotating through the levels of the frame tables --
-    // refilled by every forward that takes the path; tab_pairs: the table's own
-    // pair list (sequence i, the table's first start), kept per sequence count and start; tab_mode: the path the last
+    // refilled by every forward that takes the path; tab_pairs: the tables' own pair lists
+    // (sequence i, first start) of the wide main region, the trimmed main region and the edge
+    // segments (ensure_table), kept per sequence count, first start and max_len; tab_mode: the path the last
     // gathered forward took (vp3d_expand_table_mode), tab_depth: its frame-table depth
     // (vp3d_frame_table_depth)
     void* tab_ws = nullptr;
@@ -135,6 +136,18 @@ struct vp3d_handle {
     std::vector<int32_t> tab_pairs_host;
     int tab_mode = 0;
     int tab_depth = 0;
+    // the table rows' layout (vp3d_capi.cpp, plan_table_layout).  tab_serial: the serial number of
+    // the last forward that took a table; tab_gate (device): raised to it by that forward's bases
+    // kernel when the batch holds a start outside 0 .. max_len - 1 -- the edge launches of a trimmed
+    // layout run iff it equals theirs; tab_hint (host-mapped, two words): the serial of the last
+    // bases kernel that ran and of the last that met such a start, from which the next forward
+    // picks its layout without waiting; tab_layout: the last gathered forward's, 0 none, 1 wide,
+    // 2 trimmed (vp3d_table_layout)
+    unsigned tab_serial = 0;
+    unsigned* tab_gate = nullptr;
+    unsigned* tab_hint_host = nullptr;
+    unsigned* tab_hint_dev = nullptr;
+    int tab_layout = 0;
     // split-K workspace of conv_gemm_a4 (ConvGemmParams::sk_part / sk_flag), allocated on the
     // first forward whose plan splits a layer; flags zeroed then, each owner unit takes its
     // helpers' counts back out (and vp3d_sync_status re-zeroes them after a reported timeout)

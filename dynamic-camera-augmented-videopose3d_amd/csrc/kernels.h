@@ -50,6 +50,11 @@ struct ConvGemmParams {
     float* sk_part;
     int* sk_flag;
     int sk_full, sk_split, sk_left;
+    // conv_gemm_a4 and the f16x3 expand kernels: the launches of a trimmed table's edge segments
+    // (vp3d_capi.cpp, TablePlan) return at entry unless *gate == gate_serial, the serial of the
+    // forward whose window_bases_kernel met a start the main region does not serve.  Null: no gate.
+    const unsigned* gate;
+    unsigned gate_serial;
 };
 
 // split-K control block at byte kSplitCtlOffset of the flag area (ConvGemmParams::sk_flag)
@@ -96,6 +101,10 @@ hipError_t launch_conv_gemm_a4(const ConvGemmParams& p, Act compute, hipStream_t
 // Split-fp16 mode of conv_gemm_a4 (the q64 contract above, N % 256 == 0, >= 384 tiles); the same
 // bits as conv_gemm_q64_x3.
 bool conv_gemm_a4_x3_eligible(const ConvGemmParams& p, bool out_f32);
+// the 256 x 256 tiles of `rows` rows of N channels, and the tiles of one round (the CUs a4 fills;
+// 0 without a device)
+int64_t conv_gemm_a4_tiles(int64_t rows, int N);
+int conv_gemm_a4_round_tiles();
 hipError_t launch_conv_gemm_a4_x3(const ConvGemmParams& p, bool out_f32, hipStream_t stream);
 // Indirect windows (the expand table, vp3d_capi.cpp): with T_in < 0 the A operand's window b
 // starts at row base[b] of one shared table, base = (const int*)A + T_in (|T_in| ints in front
@@ -378,8 +387,21 @@ constexpr unsigned kFaultWindowStart = 4u;
 // base[b] = seq_b * T_tab + clamp(start_b, lo, seq_len - 1 + lead) - lo (table row 0 of a
 // sequence = start `lo`); T_tab = the rows per sequence of the table the bases are for (with
 // frame tables the deepest level's pitch)
-hipError_t launch_window_bases(const int32_t* pairs, const int32_t* seq_len, int B, int n_seq, int T_tab, int lo,
-                               int lead, int32_t* base, unsigned* fault, hipStream_t s);
+// The rows are laid out as a main region (`pitch` rows per sequence, row 0 = start `main_lo`) and,
+// in the trimmed layout (epitch > 0: main_lo = 0, main starts [0, max_len - 1]), two edge segments
+// per sequence of `epitch` rows from row `edge_row0` on: segment 2 i for the starts [lo, -1] of
+// sequence i (row 0 = start lo), segment 2 i + 1 for the starts >= max_len (row 0 = start max_len).
+// A clamped start outside [0, max_len - 1] raises *gate to `serial` (an atomic max) and stores it
+// into hint[1]; hint[0] takes `serial` from every launch (host-mapped words, either may be null).
+struct WindowRegions {
+    int pitch, main_lo, max_len;
+    int edge_row0, epitch;
+    unsigned serial;
+    unsigned* gate;
+    unsigned* hint;
+};
+hipError_t launch_window_bases(const int32_t* pairs, const int32_t* seq_len, int B, int n_seq, const WindowRegions& wr,
+                               int lo, int lead, int32_t* base, unsigned* fault, hipStream_t s);
 hipError_t launch_gather_table_rows(const void* table, const int32_t* base, int B, int T_out, int s0,
                                     int row_bytes, void* out, hipStream_t s);
 hipError_t launch_pose_metrics(const float* pred, const float* target, int64_t n_frames, int J, double* acc,

@@ -516,9 +516,34 @@ struct TablePlan {
     std::vector<int> pitch, step;
     int max_base = 0;  // the largest row base inside a sequence: clamp(start) - lo <= max_base
     bool ix_allowed = false;  // indirect windows not ruled out (copy on request, VP3D_GEMM=q64, f32 rows)
+    // The layout of the rows computed (plan_table_layout; every take-or-refuse decision above is
+    // made on the nominal, wide row count).  Wide: one main region per sequence for the starts
+    // lo .. max_len - 1 + lead (main_lo = lo, no edge segments).  Trimmed (mode 1 only): the main
+    // region serves the starts 0 .. max_len - 1 alone (main_lo = 0; T_tab / pitch[] are then its
+    // pitches), and two edge segments per sequence -- the starts lo .. -1 and max_len .. max_len
+    // - 1 + lead, `epitch[l]` rows each at level l, from row edge_row0 of every slot on -- are
+    // filled by gated launches that run only in a forward whose batch holds such a start.
+    bool trimmed = false;
+    int main_lo = 0;
+    int max_len = 0;
+    int edge_row0 = 0;
+    std::vector<int> epitch;
 };
-// table rows may number at most 1 / kTableFactor of the window rows they replace
+// Table rows may number at most 1 / kTableFactor of the window rows they replace: the margin the
+// table paths were introduced with, never measured, and kept wherever no measurement covers it --
+// a table launch shorter than one round (one round costs the same whatever its fill).  For table
+// launches of at least one round (nominal table tiles >= the CUs a4 fills) the measured rule:
+// nominal table rows <= kTableRatioNum / kTableRatioDen of the window rows
+// (profiles/r09_table_depth_crossover.txt).
 constexpr int kTableFactor = 2;
+constexpr int kTableRatioNum = 1, kTableRatioDen = 1;
+// one rule for the expand table and every frame-table level: `rows` nominal table rows of `C`
+// channels against the `wrows` window rows of the block that reads them
+bool table_pays(int64_t rows, int64_t wrows, int C) {
+    const int round = vp3d::conv_gemm_a4_round_tiles();
+    if (round <= 0 || vp3d::conv_gemm_a4_tiles(rows, C) < round) return rows <= wrows / kTableFactor;
+    return rows * kTableRatioDen <= wrows * kTableRatioNum;
+}
 
 // The f16x3 launch geometry of block layer L (k-conv, or 1x1 + residual) computed once per table
 // row: one pseudo-window per sequence at frame stride 1 over the level below -- `pitch_in` rows per
@@ -582,8 +607,9 @@ ConvGemmParams x3_probe(const Layer& L, int M, int T_out, int T_in) {
 
 // The frame-table depth of a forward whose expand table passed its own rules (tp.mode != 0, indirect
 // windows not ruled out): the deepest d <= blocks - 1 (and <= VP3D_FRAME_TABLES, which also lifts
-// the size rule) such that at every level 1 .. d the table a block reads has at most
-// 1 / kTableFactor of that block's window rows and both its launches run a4's whole / half-N /
+// the size rule) such that at every level 1 .. d the table a block reads passes the size rule
+// against that block's window rows (table_pays, on the nominal rows: those of the wide layout,
+// whichever layout is then computed) and both its launches run a4's whole / half-N /
 // quarter-N tiles (eligible without the split workspace: no split-K plan, no split-K tail, never
 // q64), and both layers of block d + 1 take indirect windows; a level whose consumer does not is
 // passed over for the next shallower one that does, down to depth 0 = plan_expand_table's own
@@ -612,7 +638,7 @@ void plan_frame_tables(const vp3d_handle* h, int B, const std::vector<int>& len,
             break;
         // the last row a window reads at this level lies inside its sequence's rows
         if ((int64_t)tp.max_base + (int64_t)(len[2 * l] - 1) * st * Lk.stride >= pout) break;
-        if (!force && (int64_t)n_seq * pin > (int64_t)B * len[2 * l - 1] / kTableFactor) break;
+        if (!force && !table_pays((int64_t)n_seq * pin, (int64_t)B * len[2 * l - 1], C)) break;
         ConvGemmParams q = x3_probe(Lk, 0, 0, 0);
         table_layer_geometry(q, Lk, n_seq, pin, st);
         ConvGemmParams r = x3_probe(Lp, 0, 0, 0);
@@ -668,8 +694,10 @@ TablePlan plan_expand_table(const vp3d_handle* h, int B, const std::vector<int>&
     // 32-bit lane offsets from the table start (conv_gemm_a4), some slack for the tiles' rebased
     // resources; one rule for both table modes
     if (bytes >= ((int64_t)1 << 31) - 65536) return tp;
-    if (!force_size && rows > (int64_t)B * len[0] / kTableFactor) return tp;
+    if (!force_size && !table_pays(rows, (int64_t)B * len[0], C)) return tp;
     tp.T_tab = (int)t_tab;
+    tp.main_lo = tp.lo;
+    tp.max_len = max_len;
     tp.max_base = max_len - 1 + gs->lead - tp.lo;
     tp.table_bytes = (size_t)bytes;
     tp.b_pad = (B + 63) / 64 * 64;
@@ -693,13 +721,85 @@ TablePlan plan_expand_table(const vp3d_handle* h, int B, const std::vector<int>&
     return tp;
 }
 
+// The layout hint: wide when the most recent forward whose bases kernel has run met a start outside
+// 0 .. max_len - 1 (the two host-mapped words of window_bases_kernel, read without waiting: a stale
+// value only picks the other correct layout), else trimmed.  VP3D_TABLE_TRIM=0|1 forces either.
+bool want_trimmed(const vp3d_handle* h) {
+    if (const char* e = getenv("VP3D_TABLE_TRIM")) return atoi(e) != 0;
+    if (!h->tab_hint_host) return true;
+    const unsigned edges = ((volatile unsigned*)h->tab_hint_host)[1];
+    const unsigned seen = ((volatile unsigned*)h->tab_hint_host)[0];
+    return !(seen != 0 && edges == seen);
+}
+
+// Which rows of the planned tables (indirect windows, mode 1; depth decided) a forward computes.
+// The wide layout of plan_expand_table spends 368 of 2,656 rows per sequence and level (max_len
+// 2,048, lead 121) on starts before frame 0 or past the last frame, which no generator makes.  The
+// trimmed layout computes the main region of the starts 0 .. max_len - 1 -- self-contained at every
+// level: level l main rows read level l - 1 main rows only -- and keeps the other starts exact
+// through the gated edge segments (TablePlan), each of which recomputes the main rows it overlaps
+// so that it is self-contained too.  Falls back to the wide layout wherever a trimmed launch would
+// leave the a4 tile forms or the rows pass the 2 GiB of the 32-bit lane offsets.
+void plan_table_layout(const vp3d_handle* h, const std::vector<int>& len, const GatherSrc* gs, int n_seq,
+                       TablePlan& tp) {
+    tp.epitch.assign((size_t)tp.depth + 1, 0);
+    if (tp.mode != 1 || !want_trimmed(h)) return;
+    const int C = h->layers[0].cout;
+    const int64_t span = (int64_t)(len[0] - 1) * tp.s0;
+    const int emax = std::max(-tp.lo, gs->lead) - 1;  // the largest start offset inside an edge segment
+    if (emax < 0) return;
+    const int64_t main0 = ((int64_t)tp.max_len + span + 15) / 16 * 16;
+    const int64_t edge0 = ((int64_t)emax + 1 + span + 15) / 16 * 16;
+    const int64_t rows = (int64_t)n_seq * (main0 + 2 * edge0);
+    if (rows * 2 * C * 2 >= ((int64_t)1 << 31) - 65536) return;
+    std::vector<int> pitch{(int)main0}, epitch{(int)edge0};
+    for (int l = 1; l <= tp.depth; ++l) {
+        const Layer &Lk = h->layers[2 * l - 1], &Lp = h->layers[2 * l];
+        const int st = tp.step[l - 1], reach = (Lk.taps - 1) * Lk.dil * st;
+        const int pout = pitch[l - 1] - reach, eout = epitch[l - 1] - reach;
+        const int64_t rd = (int64_t)(len[2 * l] - 1) * st * Lk.stride;  // rows a window steps over
+        if (pout <= 0 || eout <= 0 || tp.max_len - 1 + rd >= pout || emax + rd >= eout) return;
+        for (int edge = 0; edge < 2; ++edge) {
+            const int ns = edge ? 2 * n_seq : n_seq, pin = edge ? epitch[l - 1] : pitch[l - 1];
+            ConvGemmParams q = x3_probe(Lk, 0, 0, 0);
+            table_layer_geometry(q, Lk, ns, pin, st);
+            ConvGemmParams r = x3_probe(Lp, 0, 0, 0);
+            table_layer_geometry(r, Lp, ns, pin - reach, st);
+            table_residual_geometry(r, Lp, pin, st);
+            if (!vp3d::conv_gemm_a4_x3_eligible(q, false) || !vp3d::conv_gemm_a4_x3_eligible(r, false)) return;
+        }
+        pitch.push_back(pout);
+        epitch.push_back(eout);
+    }
+    tp.trimmed = true;
+    tp.main_lo = 0;
+    tp.T_tab = (int)main0;
+    tp.max_base = tp.max_len - 1;
+    tp.pitch = pitch;
+    tp.epitch = epitch;
+    tp.edge_row0 = (int)(n_seq * main0);
+    tp.table_bytes = (size_t)rows * 2 * C * 2;
+}
+
 // one table slot: [bases | table]; b_pad % 64 == 0 and whole 16-byte rows keep every slot aligned
 size_t table_slot_bytes(const TablePlan& tp) { return (size_t)tp.b_pad * 4 + tp.table_bytes; }
 
 // the table allocation (one slot; with frame tables three, rotating through the levels as block
 // input, k-conv output and 1x1 output, each the size of level 0) and the table's own pair list
+// -- the pair list holds the pseudo-windows of both layouts, so a change of layout uploads nothing:
+// (i, lo) of the wide main region, (i, 0) of the trimmed one, then (i, lo), (i, max_len) of the
+// edge segments -- and the gate word (device) and the two hint words (host-mapped) of the bases kernel
 int ensure_table(vp3d_handle* h, const TablePlan& tp, int n_seq, hipStream_t s) {
-    const bool same_pairs = (int)h->tab_pairs_host.size() == 2 * n_seq && (n_seq == 0 || h->tab_pairs_host[1] == tp.lo);
+    const bool same_pairs = (int)h->tab_pairs_host.size() == 8 * n_seq &&
+                            (n_seq == 0 || (h->tab_pairs_host[1] == tp.lo && h->tab_pairs_host[4 * n_seq + 3] == tp.max_len));
+    if (!h->tab_gate) {
+        HIP_TRY(hipMalloc((void**)&h->tab_gate, 256));
+        HIP_TRY(hipMemsetAsync(h->tab_gate, 0, 256, s));
+        HIP_TRY(hipHostMalloc((void**)&h->tab_hint_host, 8, hipHostMallocMapped));
+        HIP_TRY(hipHostGetDevicePointer((void**)&h->tab_hint_dev, h->tab_hint_host, 0));
+        ((volatile unsigned*)h->tab_hint_host)[0] = 0u;
+        ((volatile unsigned*)h->tab_hint_host)[1] = 0u;
+    }
     const size_t need = table_slot_bytes(tp) * (tp.depth > 0 ? 3 : 1);
     if (need > h->tab_bytes) {
         if (h->tab_ws) HIP_TRY(hipFree(h->tab_ws));
@@ -712,13 +812,17 @@ int ensure_table(vp3d_handle* h, const TablePlan& tp, int n_seq, hipStream_t s) 
         // (the device synchronised by the free: the host list is no copy's source any more)
         if (h->tab_pairs) HIP_TRY(hipFree(h->tab_pairs));
         h->tab_pairs = nullptr;
-        h->tab_pairs_host.assign((size_t)2 * n_seq, 0);
+        h->tab_pairs_host.assign((size_t)8 * n_seq, 0);
+        int32_t* const wide = h->tab_pairs_host.data();
+        int32_t *const main = wide + 2 * n_seq, *const edge = wide + 4 * n_seq;
         for (int i = 0; i < n_seq; ++i) {
-            h->tab_pairs_host[2 * i] = i;
-            h->tab_pairs_host[2 * i + 1] = tp.lo;
+            wide[2 * i] = main[2 * i] = edge[4 * i] = edge[4 * i + 2] = i;
+            wide[2 * i + 1] = edge[4 * i + 1] = tp.lo;
+            main[2 * i + 1] = 0;
+            edge[4 * i + 3] = tp.max_len;
         }
-        HIP_TRY(hipMalloc((void**)&h->tab_pairs, (size_t)2 * n_seq * 4));
-        HIP_TRY(hipMemcpyAsync(h->tab_pairs, h->tab_pairs_host.data(), (size_t)2 * n_seq * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMalloc((void**)&h->tab_pairs, (size_t)8 * n_seq * 4));
+        HIP_TRY(hipMemcpyAsync(h->tab_pairs, h->tab_pairs_host.data(), (size_t)8 * n_seq * 4, hipMemcpyHostToDevice, s));
     }
     return VP3D_OK;
 }
@@ -791,6 +895,8 @@ int vp3d_destroy(vp3d_handle* h) {
     if (h->gather_ws) hipFree(h->gather_ws);
     if (h->tab_ws) hipFree(h->tab_ws);
     if (h->tab_pairs) hipFree(h->tab_pairs);
+    if (h->tab_gate) hipFree(h->tab_gate);
+    if (h->tab_hint_host) hipHostFree(h->tab_hint_host);
     if (h->sk_ws) hipFree(h->sk_ws);
     if (h->x3_stats) hipFree(h->x3_stats);
     if (h->sk_err_host) hipHostFree(h->sk_err_host);
@@ -879,8 +985,10 @@ static int forward_impl(vp3d_handle* h, const float* x, int B, int T, float* y, 
     // the copy form costs more than the expand conv it replaces (it writes the same rows after
     // filling the table): only on request, never as the automatic choice
     if (tp.mode == 2 && !tp.forced) tp = TablePlan{};
-    GatherSrc tab_gs;
-    ConvGemmParams tab_p{};
+    // the rows computed: trimmed to the starts inside the sequences, or today's wide range
+    if (tp.mode) plan_table_layout(h, len, gs, n_seq, tp);
+    GatherSrc tab_gs, etab_gs;
+    ConvGemmParams tab_p{}, etab_p{};
     if (tp.mode) {
         // the table's fill: the expand launch itself over one pseudo-window (i, lo) of T_tab rows
         // at frame stride 1 per sequence
@@ -908,6 +1016,7 @@ static int forward_impl(vp3d_handle* h, const float* x, int B, int T, float* y, 
     if (gs) {
         h->tab_mode = tp.mode;
         h->tab_depth = tp.depth;
+        h->tab_layout = tp.mode ? (tp.trimmed ? 2 : 1) : 0;
     }
     const int buf_first = tp.mode == 1 ? 2 * tp.depth + 1 : 0;
     int rc = ensure_ws(h, B, T, dtype, buf_first);
@@ -918,13 +1027,63 @@ static int forward_impl(vp3d_handle* h, const float* x, int B, int T, float* y, 
     if (tp.mode) {
         if ((rc = ensure_table(h, tp, n_seq, s))) return rc;
         table = (char*)h->tab_ws + (size_t)tp.b_pad * 4;
-        tab_gs.pairs = h->tab_pairs;
+        tab_gs.pairs = h->tab_pairs + (tp.trimmed ? 2 * n_seq : 0);
         tab_p.Y = table;
     }
     // the table slots' tables (level 0 in slot 0; slots 1 and 2 only with frame tables)
     void* tbuf[3] = {table, nullptr, nullptr};
     if (tp.depth > 0)
         for (int i = 1; i < 3; ++i) tbuf[i] = table + i * table_slot_bytes(tp);
+    // the edge segments of a trimmed layout: the same place in every slot, after the main rows
+    const size_t edge_off = tp.trimmed ? (size_t)tp.edge_row0 * 2 * h->layers[0].cout * 2 : 0;
+    unsigned serial = 0;
+    int dslot = 0;  // the table slot the deepest level lands in (checked where it is launched)
+    if (tp.mode) {
+        if (h->tab_serial == 0xffffffffu) {
+            // the serial would wrap (the gate's atomic max needs it to grow): start over, once
+            // in 2^32 forwards, after what is in flight
+            HIP_TRY(hipStreamSynchronize(s));
+            HIP_TRY(hipMemsetAsync(h->tab_gate, 0, 256, s));
+            ((volatile unsigned*)h->tab_hint_host)[0] = 0u;
+            ((volatile unsigned*)h->tab_hint_host)[1] = 0u;
+            h->tab_serial = 0;
+        }
+        serial = ++h->tab_serial;
+        if (tp.trimmed) {
+            // the edge fill: two pseudo-windows (i, lo), (i, max_len) of epitch[0] rows per sequence
+            etab_gs = tab_gs;
+            etab_gs.pairs = h->tab_pairs + 4 * n_seq;
+            etab_p = tab_p;
+            etab_p.M = 2 * n_seq * tp.epitch[0];
+            etab_p.T_out = tp.epitch[0];
+            etab_p.Y = table + edge_off;
+            etab_p.gate = h->tab_gate;
+            etab_p.gate_serial = serial;
+            if (!expand_gemm_x3_eligible(etab_p, &etab_gs))
+                return fail(VP3D_ERR_ASSERT, "the edge fill of a trimmed expand table left the f16x3 expand kernels");
+        }
+        // The windows' bases, at the front of the forward: in front of the slot the deepest level
+        // lands in (the rotation of the layer loop below), which no table launch writes.  The same
+        // kernel opens this forward's edge launches and leaves the next forward's layout hint.
+        for (int li = 1, cur = 0, blk = -1; li <= 2 * tp.depth; ++li) {
+            int out = 0;
+            while (out == cur || out == blk) ++out;
+            if (li & 1) blk = cur;
+            cur = dslot = out;
+        }
+        vp3d::WindowRegions wr{};
+        wr.pitch = tp.pitch[tp.depth];
+        wr.main_lo = tp.main_lo;
+        wr.max_len = tp.max_len;
+        wr.edge_row0 = tp.edge_row0;
+        wr.epitch = tp.trimmed ? tp.epitch[tp.depth] : 0;
+        wr.serial = serial;
+        wr.gate = h->tab_gate;
+        wr.hint = h->tab_hint_dev;
+        const hipError_t be = launch_window_bases(gs->pairs, gs->seq_len, B, n_seq, wr, tp.lo, gs->lead,
+                                                  (int32_t*)tbuf[dslot] - tp.b_pad, h->sk_err_dev, s);
+        if (be != hipSuccess) return fail(VP3D_ERR_HIP, std::string("window bases: ") + hipGetErrorString(be));
+    }
     const Act act = dtype == VP3D_DTYPE_F32 ? Act::F32 : (dtype == VP3D_DTYPE_BF16 ? Act::BF16 : Act::F16);
     const size_t es = esize(dtype);
     const size_t buf_elems = (size_t)B * len[buf_first] * h->cfg.channels;
@@ -1030,10 +1189,8 @@ static int forward_impl(vp3d_handle* h, const float* x, int B, int T, float* y, 
             // either nothing more (block 1 reads the table through them) or the windows' rows
             // copied out into the layout the per-window expand writes
             e = launch_expand_gemm_x3(tab_p, &tab_gs, s);
-            // (with frame tables the bases go in front of the deepest level, after its launch)
-            if (e == hipSuccess && tp.depth == 0)
-                e = launch_window_bases(gs->pairs, gs->seq_len, B, n_seq, tp.T_tab, tp.lo, gs->lead, (int32_t*)h->tab_ws,
-                                        h->sk_err_dev, s);
+            // (the edge segments' fill: returns at entry unless the bases kernel opened the gate)
+            if (e == hipSuccess && tp.trimmed) e = launch_expand_gemm_x3(etab_p, &etab_gs, s);
             if (e == hipSuccess && tp.mode == 2)
                 e = launch_gather_table_rows(table, (const int32_t*)h->tab_ws, B, len[0], tp.s0, 2 * L.cout * 2, p.Y, s);
             if (tp.mode == 1) p.Y = table;  // (the next layers' input; out_buf stays free)
@@ -1096,11 +1253,25 @@ static int forward_impl(vp3d_handle* h, const float* x, int B, int T, float* y, 
                 // under VP3D_A4_SPLIT=2), and q64 is never the fallback (plan_frame_tables)
                 if (out_f32 || !conv_gemm_a4_x3_eligible(p, false))
                     return fail(VP3D_ERR_ASSERT, "frame table layer " + std::to_string(li) + " left the a4 tile forms");
+                // the deepest level lands where the bases were written in front of (dslot above)
+                if (li == 2 * tp.depth && p.Y != tbuf[dslot])
+                    return fail(VP3D_ERR_ASSERT, "the deepest frame table left the slot its window bases are in front of");
                 e = launch_conv_gemm_a4_x3(p, false, s);
-                // after the deepest level: the windows' bases in front of it, at its pitch
-                if (e == hipSuccess && li == 2 * tp.depth)
-                    e = launch_window_bases(gs->pairs, gs->seq_len, B, n_seq, p.T_out, tp.lo, gs->lead,
-                                            (int32_t*)p.Y - tp.b_pad, h->sk_err_dev, s);
+                if (e == hipSuccess && tp.trimmed) {
+                    // the same layer over the edge segments (two pseudo-windows per sequence at
+                    // their own pitch, after the main rows of the same slots), gated
+                    ConvGemmParams q = p;
+                    table_layer_geometry(q, L, 2 * n_seq, tp.epitch[L.residual ? tlevel : tlevel - 1], tp.step[tlevel - 1]);
+                    if (L.residual) table_residual_geometry(q, L, tp.epitch[tlevel - 1], tp.step[tlevel - 1]);
+                    q.A = (const char*)p.A + edge_off;
+                    q.Y = (char*)p.Y + edge_off;
+                    if (p.R) q.R = (const char*)p.R + edge_off;
+                    q.gate = h->tab_gate;
+                    q.gate_serial = serial;
+                    if (!conv_gemm_a4_x3_eligible(q, false))
+                        return fail(VP3D_ERR_ASSERT, "frame table layer " + std::to_string(li) + " (edge segments) left the a4 tile forms");
+                    e = launch_conv_gemm_a4_x3(q, false, s);
+                }
             } else if ((rc = attach_split_ws(h, p, s))) {
                 return rc;
             } else if (!(ge && strcmp(ge, "q64") == 0) &&
@@ -1259,6 +1430,20 @@ int vp3d_forward_windows_pool(vp3d_handle* h, const float* kps, int32_t f2, cons
 int vp3d_expand_table_mode(const vp3d_handle* h) { return h ? h->tab_mode : -1; }
 
 int vp3d_frame_table_depth(const vp3d_handle* h) { return h ? h->tab_depth : -1; }
+
+int vp3d_table_layout(const vp3d_handle* h, int* edges) {
+    if (!h) return -1;
+    // (the hint words are the bases kernel's: exact once the forward has completed)
+    if (edges)
+        *edges = h->tab_layout != 0 && h->tab_hint_host && ((volatile unsigned*)h->tab_hint_host)[1] == h->tab_serial;
+    return h->tab_layout;
+}
+
+void vp3d_table_depth_rule(int* factor, int* ratio_num, int* ratio_den) {
+    if (factor) *factor = kTableFactor;
+    if (ratio_num) *ratio_num = kTableRatioNum;
+    if (ratio_den) *ratio_den = kTableRatioDen;
+}
 
 int vp3d_sync_status(vp3d_handle* h, void* stream) {
     if (!h) return fail(VP3D_ERR_ARG, "handle is NULL");

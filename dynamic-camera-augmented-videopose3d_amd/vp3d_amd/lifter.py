@@ -126,10 +126,19 @@ class NativeLifter:
         Frame tables: with the expand table, blocks 1 .. d are computed once per resident frame
         position as well, as long as the table a block reads has at most half that block's
         window rows (d <= blocks - 1; the first per-window block reads the deepest table through
-        the same row bases): still the same poses, bit for bit.  The range guard then sees every
-        table row of every level.  VP3D_FRAME_TABLES=<d> forces a depth (0 = the expand table
-        only; clamped to what the kernels' conditions allow); frame_table_depth() tells the
-        depth the last call took."""
+        the same row bases): still the same poses, bit for bit.  Where a table's launch is at
+        least one round of tiles the rule is the measured one instead of "half": table rows <=
+        window rows (table_depth_rule()).  VP3D_FRAME_TABLES=<d> forces a depth (0 = the expand
+        table only; clamped to what the kernels' conditions allow); frame_table_depth() tells the
+        depth the last call took.
+
+        Trimmed layout: the tables hold the rows of the starts 0 .. max(lengths) - 1 only; starts
+        before frame 0 or past the longest sequence stay exact through edge segments whose
+        launches run only when the batch holds such a start, and such a batch makes the next
+        call compute the wide layout (every start in one region).  The range guard sees the
+        table rows computed, at every level: in the trimmed layout the rows of out-of-range
+        starts only when the batch holds one.  VP3D_TABLE_TRIM=0|1 forces wide / trimmed;
+        table_layout() tells which the last call took and whether its edge gate fired."""
         def _idx(d):
             d = torch.device(d)
             return (d.type, d.index if d.index is not None else torch.cuda.current_device())
@@ -167,6 +176,25 @@ class NativeLifter:
         """The frame-table depth of the last forward_windows: how many blocks were computed once
         per table row instead of once per window row, 0 = none (vp3d_frame_table_depth)."""
         return self._lib.vp3d_frame_table_depth(self._h)
+
+    def table_layout(self):
+        """(layout, edges) of the last forward_windows (vp3d_table_layout): layout 0 = no table,
+        1 = wide (every start lo .. max_len - 1 + lead in one region per sequence), 2 = trimmed
+        (the starts 0 .. max_len - 1; the others in gated edge segments); edges: whether its batch
+        held a start outside 0 .. max_len - 1 after the edge clamp -- in the trimmed layout,
+        whether its edge gate fired.  `edges` is valid once the forward has completed:
+        synchronise first."""
+        e = ctypes.c_int(0)
+        layout = self._lib.vp3d_table_layout(self._h, ctypes.byref(e))
+        return layout, bool(e.value)
+
+    def table_depth_rule(self):
+        """(factor, num, den) of the tables' size rule (vp3d_table_depth_rule): a table is taken
+        at nominal rows <= window rows // factor where its launch is shorter than one round of
+        tiles, at nominal rows * den <= window rows * num otherwise."""
+        f, n, d = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+        self._lib.vp3d_table_depth_rule(ctypes.byref(f), ctypes.byref(n), ctypes.byref(d))
+        return f.value, n.value, d.value
 
     # ---- f16x3 activation pre-scale ----
     def set_x3_prescale(self, p) -> None:

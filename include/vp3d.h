@@ -175,11 +175,28 @@ int vp3d_forward_windows(vp3d_handle* h, const float* kps, int32_t f2, const flo
  * same bits at every depth.  VP3D_FRAME_TABLES=<d> (read once per forward) forces a depth, also
  * past the size rule, clamped to what the other conditions allow: 0 = the expand table only, d >= 1
  * takes the expand table with it unless VP3D_EXPAND_TABLE is 0 or copy.
+ * The size rule, for the expand table and every level alike (vp3d_table_depth_rule): "at most half"
+ * where the table's launch is shorter than one round of 256 x 256 tiles; where it is at least one
+ * round, the measured rule -- nominal table rows <= the window rows (ratio 1).  Nominal rows are
+ * n_seq * T_tab as above, whichever rows are then computed:
+ * Trimmed layout: window starts that generators make lie in [0, len), so by default the tables
+ * hold the rows of the starts 0 .. max_len - 1 only (max_len + the frames a window steps over,
+ * rounded up to 16, per sequence: 14 % fewer than T_tab at max_len 2,048, lead 121).  Starts before
+ * frame 0 or from max_len on stay exact: two edge segments per sequence hold their rows, filled by
+ * launches that are enqueued with every forward and return at entry unless that forward's batch
+ * holds such a start (decided on the device: no host synchronisation).  A forward whose batch did
+ * makes the next forward on the handle take the wide layout (one region for every start, no edge
+ * segments: fewer rows than main + edges) until a batch without such starts has been seen.
+ * VP3D_TABLE_TRIM=0|1 (read once per forward) forces wide or trimmed; vp3d_table_layout reports.
+ * A forward that takes a table must not be captured into a hipGraph: its launches carry the
+ * forward's serial number as an argument, and a replay after a later forward on the handle would
+ * skip the edge launches its own bases may point into (graph capture is vp3d_forward's only).
  * What differs from vp3d_forward_windows on this path:
- *   - the f16x3 range guard (vp3d_sync_status) sees every frame of the n_seq sequences -- every
- *     table row of every level -- not only the frames some window uses: one non-finite
- *     resident frame, or an activation past the f16 range at a frame position no window
- *     reads, faults the forward;
+ *   - the f16x3 range guard (vp3d_sync_status) sees every table row computed at every level --
+ *     frame positions of the n_seq sequences whether or not a window uses them; in the trimmed
+ *     layout not the rows of starts outside 0 .. max_len - 1 unless the batch holds such a start
+ *     -- so one non-finite resident frame, or an activation past the f16 range at a frame
+ *     position no window reads, faults the forward;
  *   - a pair naming a sequence outside [0, n_seq) is a fault reported by vp3d_sync_status /
  *     the next forward (window starts outside their sequence are edge-clamped as ever). */
 int vp3d_forward_windows_pool(vp3d_handle* h, const float* kps, int32_t f2, const float* cams,
@@ -193,6 +210,18 @@ int vp3d_expand_table_mode(const vp3d_handle* h);
 /* The frame-table depth of the handle's last gathered forward: the blocks computed once per table
  * row (0 = none: the expand table at most).  -1 for a NULL handle.  (Diagnostics and tests.) */
 int vp3d_frame_table_depth(const vp3d_handle* h);
+/* Which table rows the handle's last gathered forward computed: 0 = no table, 1 = the wide
+ * layout (every start lo .. max_len - 1 + lead in one region per sequence), 2 = the trimmed layout
+ * (the starts 0 .. max_len - 1, the others in gated edge segments).  *edges (may be NULL): 1 when
+ * that forward's batch held a start outside 0 .. max_len - 1 after the edge clamp -- in the trimmed
+ * layout, when its edge gate fired; valid once the forward has completed (synchronise first).
+ * -1 for a NULL handle.  (Diagnostics and tests.) */
+int vp3d_table_layout(const vp3d_handle* h, int* edges);
+/* The size rule of the table paths: a table (the expand table, each frame-table level) is taken
+ * when its nominal rows are at most 1 / *factor of the window rows it replaces where its launch is
+ * shorter than one round of 256 x 256 tiles, and at most *ratio_num / *ratio_den of them where it
+ * is at least one round.  (Diagnostics and tests.) */
+void vp3d_table_depth_rule(int* factor, int* ratio_num, int* ratio_den);
 
 /* ---- f16x3 activation pre-scale (opt-in; no reference counterpart) ----
  * The split-fp16 path stores every activation as hi = f16(a), lo = f16(a - hi); lo is an f16
