@@ -511,6 +511,57 @@ hipError_t launch_attention(const float* QKV, int n_win, int W, int d, int heads
                             hipStream_t s);
 hipError_t launch_lstm(const LstmParams& p, hipStream_t s);
 
+// ---- CoupledLSTM training step (seq_train.hip, vp3d_seq_train.cpp) ----
+// Row (l, b, t) of the activation store: gates[(l*B + b)*T + t][4H] (activated i, f, g, o; the
+// backward overwrites it with the gate pre-activation gradients da), and the states with one
+// zero row in front of every window, cs / hs[(l*B + b)*(T+1) + t + 1][H], so that the row of
+// (b, t-1) is addressable at t = 0.
+struct LstmTrainParams {
+    const float* gin;       // layer-0 gate pre-activations [B*T][4H] (x W_ih^T + b_ih + b_hh)
+    int B, T, H, L;
+    const float* wih_t[4];  // layer l >= 1: W_ih^T [H][4H]
+    const float* whh_t[4];  // W_hh^T [H][4H]
+    const float* bias[4];   // layer l >= 1: b_ih + b_hh [4H]
+    float* gates;
+    float* cs;
+    float* hs;
+    float* hlast;           // [B][H]: the top layer's last hidden state (bn_lstm's input)
+    // nn.LSTM's inter-layer dropout: site l, element (b*T + t)*H + u, on layer l's output, l < L-1
+    float dscale;
+    uint64_t seed, thresh;
+};
+hipError_t launch_lstm_train_fwd(const LstmTrainParams& p, hipStream_t s);
+struct LstmBpttParams {
+    int B, T, H, L;
+    const float* wih[4];    // layer l >= 1: W_ih, torch layout [4H][H]
+    const float* whh[4];    // W_hh [4H][H]
+    float* gates;           // in: activated gates; out: da rows
+    const float* cs;
+    const float* dhlast;    // [B][H]: gradient of the top layer's last hidden state
+    float dscale;
+    uint64_t seed, thresh;
+};
+hipError_t launch_lstm_bptt(const LstmBpttParams& p, hipStream_t s);
+// out[(b*T + t)][u] = dropout_site(h[(b*(T+1) + t + 1)][u]): layer `site`'s output rows as layer
+// site + 1 read them (the operand of its dW_ih)
+hipError_t launch_lstm_drop_rows(const float* hs, int B, int T, int H, float p, uint64_t seed, int site, float* out,
+                                 hipStream_t s);
+hipError_t launch_vec_add(const float* a, const float* b, int n, float* out, hipStream_t s);
+// the head's rows (M = B): Y = X W^T + bias (W torch layout [N][K]); dX = dY W
+hipError_t launch_head_linear(const float* X, const float* W, const float* bias, int M, int N, int K, float* Y,
+                              hipStream_t s);
+hipError_t launch_head_linear_dgrad(const float* dY, const float* W, int M, int N, int K, float* dX, hipStream_t s);
+// Y = dropout(leaky(Z * alpha + shift)), leaky(v) = v > 0 ? v : slope * v (slope 1: the plain
+// BatchNorm bn_lstm); mask element m*C + c of `site`; any C
+hipError_t launch_bn_leaky_fwd(const float* Z, int M, int C, const float* alpha, const float* shift, float slope,
+                               float p, uint64_t seed, int site, float* Y, hipStream_t s);
+// its backward, with the BatchNorm (batch statistics) backward as launch_bn_train_backward forms
+// it: dgamma / dbeta (either may be null), coef [3][C] scratch, dZ
+hipError_t launch_bn_leaky_bwd(const float* dO, const float* Z, int M, int C, const float* gamma, const float* alpha,
+                               const float* shift, const float* mean, const float* invstd, float slope, float p,
+                               uint64_t seed, int site, float* coef, float* dgamma, float* dbeta, float* dZ,
+                               hipStream_t s);
+
 // ---- StackedPoseLifter MLP, eval mode (stacked_lifter.hip, vp3d_stacked.cpp) ----
 constexpr int kStackedMaxLinear = 10;  // num_layers <= 8 hidden Linears + the first and the last
 struct StackedParams {

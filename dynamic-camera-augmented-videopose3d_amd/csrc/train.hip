@@ -14,6 +14,7 @@
 // arithmetic is f32 (the reference trains in fp32); per-channel reductions are
 // accumulated in f64.
 #include <climits>
+#include "dropout_hash.h"
 #include "kernels.h"
 
 #pragma clang fp contract(off)
@@ -29,17 +30,7 @@ __device__ __forceinline__ bf16x4 to_bf16x4(f32x4 v) {
     return bf16x4{(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
 }
 
-// ---------------------------------------------------------------------------
-// dropout keep mask: counter-based (splitmix64 of seed, layer, element), so the
-// backward regenerates the mask instead of storing it
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ bool drop_keep(uint64_t seed, int layer, int64_t idx, uint64_t thresh) {
-    uint64_t z = seed + (uint64_t)(layer + 1) * 0x9E3779B97F4A7C15ull + (uint64_t)idx * 0xD1B54A32D192ED03ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return (z >> 32) < thresh;
-}
+// dropout keep mask: drop_keep / keep_threshold (dropout_hash.h)
 
 // ---------------------------------------------------------------------------
 // weight packing (per step: the optimiser changes the torch-layout weights)
@@ -519,12 +510,6 @@ inline int grid_for(int64_t work, int per_block = 256, int cap = 65536) {
     int64_t g = (work + per_block - 1) / per_block;
     if (g < 1) g = 1;
     return (int)(g < cap ? g : cap);
-}
-
-inline uint64_t keep_threshold(float p) {
-    if (p <= 0.f) return 1ull << 32;
-    const double keep = 1.0 - (double)p;
-    return (uint64_t)(keep * 4294967296.0);
 }
 
 // rows per chunk of a column reduction: enough chunks to fill the chip, >= 64 rows each

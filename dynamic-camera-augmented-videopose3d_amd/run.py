@@ -2,16 +2,19 @@
 """Training and evaluation driver of the temporal-lifter path (drop-in for the FCN
 branch of the reference's run.py: :290-309 model build, :400-417 device and
 checkpoint, :424-590 the training loop, :653-673 its entry, :862-995 per-action
-evaluation), and the --evaluate path of the fork's trajectory lifters
+evaluation), the --evaluate path of the fork's trajectory lifters
 (--use-model Transformer | LSTM-Coupled: :311-363 model build, :712-713 the
 sliding_window dispatch) and of the ensemble (--use-model StackedPoselifter: :241-288 the
 three models and their checkpoints, :714-729 the MLP on the transformer's and the FCN's
-predictions, :985-987 the two diff lines).
+predictions, :985-987 the two diff lines), and training of --use-model LSTM-Coupled
+(:337-338 window and pad, :470-471 the model call; the other trajectory lifters and the
+ensemble do not train here).
 
     python run.py -e 60 -c checkpoint --subjects-train S1,S2 --subjects-test S3   # train
     python run.py --evaluate synthetic --fcn-architecture 3,3,3 --subjects-test '*'
     python run.py --evaluate epoch_60.bin -c checkpoint --causal --compute-dtype bf16
     python run.py --use-model Transformer --evaluate epoch_80.bin -c checkpoint -d CMU
+    python run.py --use-model LSTM-Coupled -e 80 -c checkpoint -d CMU              # train the LSTM
     python run.py --use-model StackedPoselifter --evaluate stacked.bin -c checkpoint \
         --transformer-weights tr.bin --fcn-weights fcn.bin
 
@@ -318,13 +321,21 @@ def fetch(data, subjects, action_filter=None):
 
 def train(args, n_epochs, train_generator, test_generator, model_pos_train, model_pos, optimizer,
           lr, lr_decay, save_state=True, resume=None, log=print):
-    """The reference's epoch loop (run.py:424-590) for the temporal FCN: per batch the
-    train-mode forward, mpjpe, backward and Adam step on the MI355X; per epoch the
-    evaluation of the copied weights on the test generator, the exponential lr decay, the
+    """The reference's epoch loop (run.py:424-590) for the temporal FCN and for CoupledLSTM:
+    per batch the train-mode forward, mpjpe, backward and Adam step on the MI355X; per epoch
+    the evaluation of the copied weights on the test generator, the exponential lr decay, the
     BatchNorm momentum decay 0.1 -> 0.001 and the checkpoint.  Returns the per-epoch
-    (train, valid) losses in metres and the best validation error."""
+    (train, valid) losses in metres and the best validation error.
+
+    A trajectory lifter (--use-model LSTM-Coupled) gets (batch_2d, batch_cam) per batch
+    (run.py:470-471) and is validated by sliding_window over the test sequences, as --evaluate
+    does (run.py:712-713).  Its BatchNorm momentum stays put: the reference decays it for
+    TemporalModelBase only (run.py:554).  torch's generator, from which the model draws its
+    dropout-mask seeds, is re-seeded from (--seed, epoch) at every epoch, so that --resume
+    reproduces the uninterrupted run."""
     from common.loss import mpjpe
 
+    seq = args.model_name in SEQ_MODELS
     losses_train, losses_valid = [], []
     epoch = 0
     initial_momentum, final_momentum = 0.1, 0.001
@@ -340,8 +351,10 @@ def train(args, n_epochs, train_generator, test_generator, model_pos_train, mode
         sum_train = 0.0
         N = 0
         model_pos_train.train()
+        if seq:
+            torch.manual_seed(args.seed * 1000003 + epoch)
         for batch_cam, batch_3d, batch_2d in train_generator.next_epoch():
-            pred = model_pos_train(batch_2d)
+            pred = model_pos_train(batch_2d, batch_cam) if seq else model_pos_train(batch_2d)
             loss = mpjpe(pred, batch_3d)
             optimizer.zero_grad()
             loss.backward()
@@ -357,7 +370,11 @@ def train(args, n_epochs, train_generator, test_generator, model_pos_train, mode
                 sum_valid = 0.0
                 N = 0
                 for batch_cam, batch_3d, batch_2d, _ in test_generator():
-                    loss = mpjpe(model_pos(batch_2d), batch_3d)
+                    if seq:
+                        pred = model_pos.sliding_window(batch_2d, batch_cam, SEQ_RECEPTIVE_FIELD)
+                    else:
+                        pred = model_pos(batch_2d)
+                    loss = mpjpe(pred, batch_3d)
                     n = batch_3d.shape[0] * batch_3d.shape[1]
                     sum_valid += n * loss.item()
                     N += n
@@ -374,7 +391,8 @@ def train(args, n_epochs, train_generator, test_generator, model_pos_train, mode
             group["lr"] *= lr_decay
         epoch += 1
         momentum = initial_momentum * np.exp(-epoch / args.epochs * np.log(initial_momentum / final_momentum))
-        model_pos_train.set_bn_momentum(momentum)
+        if not seq:
+            model_pos_train.set_bn_momentum(momentum)
         if save_state and epoch % args.checkpoint_frequency == 0:
             os.makedirs(args.checkpoint, exist_ok=True)
             path = os.path.join(args.checkpoint, 'epoch_{}.bin'.format(epoch))
@@ -386,7 +404,9 @@ def train(args, n_epochs, train_generator, test_generator, model_pos_train, mode
 
 def train_main(args, data):
     """`run.py` without --evaluate (run.py:653-673): ChunkedGenerator batches of
-    batch_size // stride chunks of `stride` frames, Adam(lr, amsgrad=True), train()."""
+    batch_size // stride chunks of `stride` frames, Adam(lr, amsgrad=True), train().
+    --use-model LSTM-Coupled trains the CoupledLSTM the same way (windows of 243 frames, one
+    predicted frame each; seq_train_refusal lists what it does not take)."""
     from common.generators import ChunkedGenerator, UnchunkedGenerator
     from vp3d_amd.train import Adam
 
@@ -397,11 +417,20 @@ def train_main(args, data):
     print("Training Subjects: ", ", ".join(subjects_train))
     print("Test Subjects: ", ", ".join(subjects_test))
     j2, j3 = joint_counts(data)
-    model_pos_train = build_model(args, j2, J_out=j3).cuda()
-    # --train-dtype: the training step only; the per-epoch evaluation model keeps --compute-dtype
-    model_pos_train.set_train_dtype(getattr(args, "train_dtype", "fp32"))
-    model_pos = build_model(args, j2, announce=False, J_out=j3).cuda()
-    pad = (model_pos.receptive_field() - 1) // 2
+    seq = args.model_name in SEQ_MODELS
+    if seq:
+        # torch's default init (run.py:334-347 builds the model as constructed), reproducible
+        # under --seed; the native training step is opt-in per model
+        torch.manual_seed(args.seed)
+        model_pos_train = build_model(args, j2, J_out=j3).cuda().enable_native_training()
+        model_pos = build_model(args, j2, announce=False, J_out=j3).cuda()
+        pad = (SEQ_RECEPTIVE_FIELD - 1) // 2  # run.py:337-338: receptive field 243, pad 121
+    else:
+        model_pos_train = build_model(args, j2, J_out=j3).cuda()
+        # --train-dtype: the training step only; the per-epoch evaluation model keeps --compute-dtype
+        model_pos_train.set_train_dtype(getattr(args, "train_dtype", "fp32"))
+        model_pos = build_model(args, j2, announce=False, J_out=j3).cuda()
+        pad = (model_pos.receptive_field() - 1) // 2
     causal_shift = pad if args.causal else 0
     # `data` is undecimated here: the training views get the reference fetch's --subset /
     # --downsample rule (run.py:168-180, fetch(..., subset=args.subset) at :656), the test
@@ -432,6 +461,28 @@ def train_main(args, data):
     # is parsed and unused) and the logged lr starts at train()'s default 0.001.
     return train(args, args.epochs, train_generator, test_generator, model_pos_train, model_pos, optimizer,
                  0.001, 0.95, save_state=True, resume=resume)
+
+
+def seq_train_refusal(args):
+    """Why run.py cannot train --use-model Transformer | LSTM-Coupled | LSTM-Uncoupled at these
+    arguments, or None (also with --evaluate).  Checked before any model is built (and before
+    the device is looked for).  Only LSTM-Coupled trains here (vp3d_amd.seq_train)."""
+    if args.evaluate:
+        return None
+    name = f"--use-model {args.model_name}"
+    if args.model_name != "LSTM-Coupled":
+        return (f"{name}: training this trajectory lifter is outside the MI355X path (SURVEY.md §8(f)); "
+                "--evaluate runs it, and --use-model LSTM-Coupled trains")
+    if args.stride != 1:
+        return f"{name}: training predicts one frame per window (--stride 1, not {args.stride})"
+    if args.trajectory:
+        return f"{name}: training takes the camera matrices itself (no --trajectory)"
+    if args.compute_dtype != "fp32" or getattr(args, "train_dtype", "fp32") != "fp32":
+        return f"{name}: training runs in fp32 (--compute-dtype fp32, --train-dtype fp32)"
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        return (f"{name}: training runs on one device (BatchNorm statistics are per device; WORLD_SIZE = "
+                f"{os.environ['WORLD_SIZE']})")
+    return None
 
 
 def x3_calibrate_refusal(args):
@@ -484,11 +535,10 @@ def main(argv=None):
         raise SystemExit(stacked_refusal(args))
     if x3_calibrate_refusal(args):
         raise SystemExit(x3_calibrate_refusal(args))
+    if seq_model and seq_train_refusal(args):
+        raise SystemExit(seq_train_refusal(args))
     if not torch.cuda.is_available():
         raise SystemExit("run.py evaluates on the MI355X (no CPU fallback)")
-    if seq_model and not args.evaluate:
-        raise SystemExit(f"--use-model {args.model_name}: training the trajectory lifters is outside the "
-                         "MI355X path (SURVEY.md §8(f)); --evaluate runs them")
     if seq_model and (args.trajectory or args.compute_dtype != "fp32"):
         raise SystemExit(f"--use-model {args.model_name} takes the camera matrices itself and runs in fp32 "
                          "(no --trajectory, --compute-dtype fp32)")

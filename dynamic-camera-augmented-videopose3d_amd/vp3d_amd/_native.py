@@ -69,6 +69,8 @@ EXPORTS = [
     "vp3d_train_dropout_mask", "vp3d_train_relu_mask", "vp3d_train_layer_rows", "vp3d_train_reduce_doubles", "vp3d_adam_step", "vp3d_mpjpe_backward",
     "vp3d_seq_weight_count", "vp3d_seq_create", "vp3d_seq_destroy", "vp3d_seq_forward",
     "vp3d_seq_sliding_window",
+    "vp3d_seq_trainer_create", "vp3d_seq_trainer_destroy", "vp3d_seq_train_forward", "vp3d_seq_train_backward",
+    "vp3d_seq_train_mask", "vp3d_seq_train_bytes", "vp3d_seq_train_profile",
     "vp3d_stacked_weight_count", "vp3d_stacked_create", "vp3d_stacked_forward", "vp3d_stacked_destroy",
 ]
 
@@ -239,6 +241,14 @@ _SIGNATURES = {
     "vp3d_seq_destroy": (_int, [_vp]),
     "vp3d_seq_forward": (_int, [_vp, _vp, _vp, _int, _int, _vp, _vp]),
     "vp3d_seq_sliding_window": (_int, [_vp, _vp, _vp, _int, _int, _vp, _vp]),
+    "vp3d_seq_trainer_create": (_int, [ctypes.POINTER(vp3d_seq_cfg), ctypes.POINTER(_vp)]),
+    "vp3d_seq_trainer_destroy": (_int, [_vp]),
+    "vp3d_seq_train_forward": (_int, [_vp, ctypes.POINTER(_vp), _int, _vp, _vp, _int, _int, ctypes.c_float,
+                                      ctypes.POINTER(ctypes.c_double), ctypes.c_uint64, _vp, _vp]),
+    "vp3d_seq_train_backward": (_int, [_vp, ctypes.POINTER(_vp), _int, _vp, ctypes.POINTER(_vp), _vp]),
+    "vp3d_seq_train_mask": (_int, [_vp, _int, _int, _i64, _vp, _vp]),
+    "vp3d_seq_train_bytes": (_i64, [ctypes.POINTER(vp3d_seq_cfg), _int, _int]),
+    "vp3d_seq_train_profile": (_int, [_vp, _int, ctypes.POINTER(ctypes.c_double)]),
     "vp3d_stacked_weight_count": (_int, [ctypes.POINTER(vp3d_stacked_cfg)]),
     "vp3d_stacked_create": (_int, [ctypes.POINTER(vp3d_stacked_cfg), ctypes.POINTER(_vp), _int,
                                    ctypes.POINTER(_vp)]),

@@ -21,8 +21,8 @@ BUILD_DIR = os.path.join(ROOT_PKG, "build")
 LIB_PATH = os.path.join(PKG_DIR, "libvp3d.so")
 
 SOURCES = ["conv_gemm.hip", "conv_gemm_big.hip", "conv_gemm_8p.hip", "conv_gemm_q64.hip", "conv_gemm_a4.hip", "conv_gemm_tail.hip", "expand_gemm.hip", "expand_table.hip", "preprocess.hip",
-           "metrics.hip", "act_stats.hip", "stream_step.hip", "stream_persist.hip", "stream_pipe.hip", "stream_batch.hip", "train.hip", "train_bf16.hip", "seq_lifter.hip", "stacked_lifter.hip", "vp3d_capi.cpp", "vp3d_train.cpp",
-           "vp3d_seq.cpp", "vp3d_stacked.cpp"]
+           "metrics.hip", "act_stats.hip", "stream_step.hip", "stream_persist.hip", "stream_pipe.hip", "stream_batch.hip", "train.hip", "train_bf16.hip", "seq_lifter.hip", "seq_train.hip", "stacked_lifter.hip", "vp3d_capi.cpp", "vp3d_train.cpp",
+           "vp3d_seq.cpp", "vp3d_seq_train.cpp", "vp3d_stacked.cpp"]
 ARCH = os.environ.get("VP3D_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 

@@ -624,6 +624,71 @@ int vp3d_seq_forward(vp3d_seq_lifter* h, const float* x2d, const float* xcam, in
 int vp3d_seq_sliding_window(vp3d_seq_lifter* h, const float* x2d, const float* xcam, int L, int window, float* y,
                             void* stream);
 
+/* ---- CoupledLSTM training step (opt-in; run.py:451-487 with --use-model LSTM-Coupled) ----
+ * The reference trains CoupledLSTM (common/models/CamLSTM.py:47-129) in train mode inside
+ * run.py's loop (:451-487: model(batch_2d, batch_cam) :470-471, mpjpe, loss.backward(),
+ * optim.Adam(amsgrad=True).step() :662): nn.LSTM with its inter-layer dropout, bn_lstm and the
+ * head's BatchNorm1d on batch statistics with a running-stat update, LeakyReLU(0.01), Dropout.
+ * A seq trainer runs that forward and its backward through time on the device in f32, following
+ * vp3d_trainer's conventions: the parameters stay in caller-owned device memory and are passed
+ * per call as a table of device pointers in vp3d_seq_weight_count order (the running statistics
+ * among them, updated in place); dropout masks come from the counter hash of (seed, site,
+ * element) and are regenerated in the backward, never stored.  Mask sites: 0 .. L-2 the
+ * inter-layer LSTM dropouts (element (b, t, u), CamLSTM.py:77 nn.LSTM(dropout=)), then one per
+ * head layer (element (b, c), CamLSTM.py:91). */
+typedef struct vp3d_seq_trainer vp3d_seq_trainer;
+
+/* kind must be VP3D_SEQ_LSTM (the transformer kind is VP3D_ERR_ARG: its training is not built);
+ * hidden size 64 or 128, 1..4 cells, as vp3d_seq_create. */
+int vp3d_seq_trainer_create(const vp3d_seq_cfg* cfg, vp3d_seq_trainer** out);
+int vp3d_seq_trainer_destroy(vp3d_seq_trainer* t);
+
+/* Train-mode forward (CoupledLSTM.forward in train mode, CamLSTM.py:104-129).  params: host
+ * array of n_params DEVICE pointers, vp3d_seq_weight_count order.  x2d device f32
+ * (B, T, J_in, F), xcam device f32 (B, T, 3, 4) -> y device f32 (B, 1, J_out, out_features).
+ * dropout_p: the module's dropout (nn.LSTM's inter-layer one and the head's nn.Dropout), in
+ * [0, 1) else VP3D_ERR_ARG.  momenta: one BatchNorm1d.momentum per BatchNorm (bn_lstm, then the
+ * head's), host doubles.  B >= 2 (batch statistics; B = 1 is VP3D_ERR_ARG), T >= 1.  The
+ * activation store (vp3d_seq_train_bytes) is allocated on first use and grown on demand; a
+ * failed allocation is VP3D_ERR_OOM with a message.  Kept until the next forward. */
+int vp3d_seq_train_forward(vp3d_seq_trainer* t, float* const* params, int n_params, const float* x2d,
+                           const float* xcam, int B, int T, float dropout_p, const double* momenta, uint64_t seed,
+                           float* y, void* stream);
+
+/* Backward of the latest vp3d_seq_train_forward (loss.backward(), run.py:477; same params).
+ * dy: device f32 like y.  grads: host array of n_params device pointers; each non-NULL
+ * trainable entry is overwritten with its gradient in torch layout, NULL entries are skipped,
+ * running-stat entries are ignored.  The input gradient is not formed (the inputs are data).
+ * VP3D_ERR_STATE without a preceding forward (the backward consumes the stored gates: one
+ * backward per forward). */
+int vp3d_seq_train_backward(vp3d_seq_trainer* t, float* const* params, int n_params, const float* dy,
+                            float* const* grads, void* stream);
+
+/* Test hook, for the latest forward: which = 0 the dropout keep mask (1 = kept) of `site`,
+ * which = 1 the LeakyReLU side (1 = BN output > 0; head sites only).  Sites 0 .. L-2 are the
+ * inter-layer LSTM dropouts, n = B * T * H, row-major (b, t, u); sites L-1 .. are the head
+ * layers, n = B * width, row-major (b, c).  out: device uint8. */
+int vp3d_seq_train_mask(vp3d_seq_trainer* t, int site, int which, int64_t n, uint8_t* out, void* stream);
+
+/* Bytes of the activation store of a (B, T) forward: per (window, step, cell) the four
+ * activated gates, the cell state and the hidden state, B * T * L * 6 H * 4 (1.53 GB at
+ * B = 1024, T = 243, L = 2, H = 128).  The trainer's one device allocation is larger, about 1.5
+ * times that at the shape above: on top come layer 0's gate pre-activations (B * T * 4 H floats,
+ * 0.51 GB there), the input rows (B * T * (J_in * F + 12) floats, 0.05 GB), with two or more
+ * cells one scratch copy of a cell's dropped output rows (B * T * H floats, 0.13 GB), a zero
+ * row per (window, cell) in front of c and h, 64 MB of weight-gradient partials, and the head's
+ * B rows.  Host arithmetic only; -1 for an invalid configuration or non-positive B or T. */
+int64_t vp3d_seq_train_bytes(const vp3d_seq_cfg* cfg, int B, int T);
+
+/* Measurement (tools/bench_lstm_train.py), as vp3d_train_profile: synchronises; `ms` (may be
+ * NULL) receives the device milliseconds, summed since the previous call, of [0] the recurrence
+ * forward, [1] the backward through time, [2] the cells' weight-gradient GEMMs and bias column
+ * sums, [3] the rest (weight packs, input rows and projection, the head, the dropped rows).
+ * Then profiling is switched on or off.  While on, every launch group is bracketed by two
+ * events that are kept until the next call of this function: switch it on for a measurement
+ * pass of a few steps, not for a training run. */
+int vp3d_seq_train_profile(vp3d_seq_trainer* t, int on, double* ms);
+
 /* ---- stacked pose lifter: the ensemble MLP, eval mode ----
  * StackedPoseLifter (common/models/StackedPoseLifter.py:4-56; built at run.py:241-288, called
  * per sequence at run.py:719-720): Linear(2 J F -> layer_size), ReLU, Dropout, num_layers x
