@@ -158,12 +158,16 @@ __device__ unsigned long long* g_a4_trace;
 // output keeps the whole tile's K order, so the same bits as a 256 x 256 tile.
 // HNL = 2 (quarter-N, f16x3 only): 256 x 64 tiles, each wave 128 x 32, for tails of <= a
 // quarter round.
-template <typename CT, int ABL, int X3 = 0, bool GD = true, bool SPLIT = false, int HNL = 0, bool IX = false>
+// YP (pitched output, ConvGemmParams::Y_T > 0; f16x3 split rows out, direct windows): output row m
+// lands at row out_row(m) of Y -- the epilogue's store offsets alone differ.
+template <typename CT, int ABL, int X3 = 0, bool GD = true, bool SPLIT = false, int HNL = 0, bool IX = false,
+          bool YP = false>
 __global__ __launch_bounds__(256, 1) void conv_gemm_a4(ConvGemmParams p_arg) {
     constexpr bool HN = HNL > 0;
     static_assert(!HN || (GD && !SPLIT), "half-N tiles: grouped pieces, no split");
     static_assert(HNL < 2 || X3 != 0, "quarter-N tiles: the split-fp16 epilogue only");
     static_assert(!IX || (X3 == 1 && GD && !SPLIT), "indirect windows: the split-fp16 whole / half-N / quarter-N tiles");
+    static_assert(!YP || (X3 == 1 && GD && !SPLIT && !IX), "pitched output: the split-fp16 whole / half-N / quarter-N tiles");
     constexpr int TN = GN >> HNL;  // tile channels
     constexpr int NJ = TN / 32;    // channel blocks of 16 per wave (two wave columns)
     constexpr int WP = TN / 32;    // W pieces per wave and K-tile (TN rows x 128 B, 4 waves)
@@ -654,6 +658,7 @@ __global__ __launch_bounds__(256, 1) void conv_gemm_a4(ConvGemmParams p_arg) {
         // across it (past 256 VGPRs, into the accumulator file)
         launder_lane_consts(prow, lc, fsw, fo0, fo1, a_base, w_base, grp, c0);
         launder_params(p);
+        if constexpr (YP) launder_s(p.Y_T);
         const int next = HN ? nunits : tix + (int)gridDim.x;  // (HN: one unit per workgroup)
         const bool has_next = next < nunits;
         res0 = lres ? 0 : -1;
@@ -930,9 +935,24 @@ __global__ __launch_bounds__(256, 1) void conv_gemm_a4(ConvGemmParams p_arg) {
                     sh[j][0] = f32x2{h4[0], h4[1]};
                     sh[j][1] = f32x2{h4[2], h4[3]};
                 }
+                // YP: the row's place from the tile's first output row at the output pitch, walked
+                // down the lane's eight rows (16 apart; T_out >= 16: at most one window boundary a
+                // step) from two divisions per half -- ypr: the row inside its window, yr: the place
+                int ypr = 0, yr = 0;
+                if constexpr (YP) {
+                    const int mf = em0 + ewr * 128 + er16;
+                    const int yb = mf / p.T_out, yb0 = em0 / p.T_out;
+                    ypr = mf - yb * p.T_out;
+                    yr = (yb - yb0) * p.Y_T + ypr - (em0 - yb0 * p.T_out);
+                }
                 static_for<8>([&](auto i_c) __attribute__((always_inline)) {
                     constexpr int I = decltype(i_c)::value;
                     const int m = em0 + ewr * 128 + 16 * I + er16;
+                    if constexpr (YP && I > 0) {
+                        const bool wrap = ypr + 16 >= p.T_out;
+                        ypr += wrap ? 16 - p.T_out : 16;
+                        yr += wrap ? 16 + p.Y_T - p.T_out : 16;
+                    }
                     float v4[4][4];  // [block j][element]: BN + ReLU, accumulator layout
                     static_for<NB>([&](auto j_c) __attribute__((always_inline)) {
                         constexpr int J = decltype(j_c)::value;
@@ -993,8 +1013,11 @@ __global__ __launch_bounds__(256, 1) void conv_gemm_a4(ConvGemmParams p_arg) {
                             // (per 8 values: a running max over the half costs a VGPR the K
                             // loop does not have)
                             gemm::x3_range_flag(in ? t : 0.f, p.scale, p.N);
-                            const uint32_t yo =
-                                in ? (uint32_t)(((size_t)(m - em0) * p.ldy + 2 * nw + 64 * jp + ec0) * 2) : 0xFFFFFF00u;
+                            uint32_t yo;
+                            if constexpr (YP)
+                                yo = in ? (uint32_t)(((size_t)yr * p.ldy + 2 * nw + 64 * jp + ec0) * 2) : 0xFFFFFF00u;
+                            else
+                                yo = in ? (uint32_t)(((size_t)(m - em0) * p.ldy + 2 * nw + 64 * jp + ec0) * 2) : 0xFFFFFF00u;
                             if constexpr ((ABL & 16) != 0) {  // (measurement builds: no output stores)
                                 asm volatile("" ::"v"(oh), "v"(ol));
                             } else {
@@ -1007,6 +1030,11 @@ __global__ __launch_bounds__(256, 1) void conv_gemm_a4(ConvGemmParams p_arg) {
             };
             auto y_rsrc_of = [&]() __attribute__((always_inline)) {
                 // the output resource starts at the tile's first row (outputs past 2^31 bytes)
+                if constexpr (YP) {  // (rows at the output pitch, out_row)
+                    const int yrow0 = out_row(p, em0);
+                    const size_t y_rest = (size_t)(out_row(p, p.M - 1) + 1 - yrow0) * p.ldy * OB;
+                    return make_rsrc((const char*)p.Y + (size_t)yrow0 * p.ldy * OB, clamp_range31(y_rest));
+                }
                 const size_t y_rest = (size_t)(p.M - em0) * p.ldy * OB;
                 return make_rsrc((const char*)p.Y + (size_t)em0 * p.ldy * OB,
                                  clamp_range31(y_rest));
@@ -1411,6 +1439,19 @@ bool conv_gemm_a4_x3_indirect_ok(const ConvGemmParams& p, bool any_fill) {
     return q.sk_split <= 1;
 }
 
+// an f16x3 1x1 + residual layer with an output window pitch (Y_T > 0) runs on a4's whole / half-N
+// / quarter-N tiles alone: direct windows, and no split workspace attached, so that neither a
+// split-K plan nor the split-K tail (which address their output rows themselves) is planned
+bool conv_gemm_a4_x3_pitched_ok(const ConvGemmParams& p) {
+    // (T_out >= 16: the epilogue walks a lane's rows, 16 apart, over one window boundary a step)
+    if (p.Y_T < p.T_out || p.T_out < 16 || p.M <= 0 || p.R == nullptr || a4_indirect(p)) return false;
+    if (p.sk_part != nullptr || p.sk_flag != nullptr) return false;
+    // (32-bit row indices, and store offsets from a tile's first row, at the output pitch)
+    const int64_t yrows = ((int64_t)(p.M - 1) / p.T_out) * p.Y_T + p.T_out;
+    if (yrows * p.ldy * 2 >= ((int64_t)1 << 31) - 65536) return false;
+    return a4_x3_shape_ok(p, false);
+}
+
 bool conv_gemm_a4_fills(const ConvGemmParams& p) {
     const int ntiles = ((p.M + GM - 1) / GM) * (p.N / GN);
     if (ntiles >= 384) return true;
@@ -1432,7 +1473,7 @@ static void a4_launch(const ConvGemmParams& p, dim3 grid, bool split, hipStream_
 
 // the whole rounds (M-tiles below ntm - mt_tail, if any; walked by one workgroup per CU when
 // `walk_cus` > 0) then the tail as half-N units
-template <typename CT, int X3, bool IX = false>
+template <typename CT, int X3, bool IX = false, bool YP = false>
 static void a4_launch_whole(const ConvGemmParams& p, int mt0, hipStream_t stream, int walk_cus) {
     if (mt0 > 0) {
         ConvGemmParams q = p;
@@ -1440,26 +1481,26 @@ static void a4_launch_whole(const ConvGemmParams& p, int mt0, hipStream_t stream
         q.sk_split = q.sk_full = q.sk_left = 0;
         const int tiles = mt0 * (p.N / GN);
         const dim3 g(walk_cus > 0 && tiles > walk_cus ? walk_cus : tiles);
-        hipLaunchKernelGGL((conv_gemm_a4<CT, 0, X3, true, false, 0, IX>), g, dim3(256), 0, stream, q);
+        hipLaunchKernelGGL((conv_gemm_a4<CT, 0, X3, true, false, 0, IX, YP>), g, dim3(256), 0, stream, q);
     }
 }
 
-template <typename CT, int X3, bool IX = false>
+template <typename CT, int X3, bool IX = false, bool YP = false>
 static void a4_launch_hn(const ConvGemmParams& p, int mt_tail, hipStream_t stream, int walk_cus = 0, int level = 1) {
     const int ntm = (p.M + GM - 1) / GM;
     const int mt0 = ntm - mt_tail;
-    a4_launch_whole<CT, X3, IX>(p, mt0, stream, walk_cus);
+    a4_launch_whole<CT, X3, IX, YP>(p, mt0, stream, walk_cus);
     ConvGemmParams t = p;
     t.sk_split = t.sk_left = 0;
     t.sk_full = mt0;  // the HN launch's first M-tile
     if constexpr (X3 != 0) {
         if (level == 2) {
-            hipLaunchKernelGGL((conv_gemm_a4<CT, 0, X3, true, false, 2, IX>), dim3(mt_tail * (p.N / (GN / 4))), dim3(256),
+            hipLaunchKernelGGL((conv_gemm_a4<CT, 0, X3, true, false, 2, IX, YP>), dim3(mt_tail * (p.N / (GN / 4))), dim3(256),
                                0, stream, t);
             return;
         }
     }
-    hipLaunchKernelGGL((conv_gemm_a4<CT, 0, X3, true, false, 1, IX>), dim3(mt_tail * (p.N / (GN / 2))), dim3(256), 0,
+    hipLaunchKernelGGL((conv_gemm_a4<CT, 0, X3, true, false, 1, IX, YP>), dim3(mt_tail * (p.N / (GN / 2))), dim3(256), 0,
                        stream, t);
 }
 
@@ -1485,12 +1526,20 @@ hipError_t launch_conv_gemm_a4_x3(const ConvGemmParams& p_in, bool out_f32, hipS
     // whole, half-N and quarter-N tiles of the split rows form only
     const bool ix = a4_indirect(p);
     if (ix && (out_f32 || !conv_gemm_a4_x3_indirect_ok(p, true))) return hipErrorInvalidValue;
+    // pitched output (ConvGemmParams::Y_T; the caller asked conv_gemm_a4_x3_pitched_ok): the
+    // same tile forms, the 1x1 + residual layers over direct windows only
+    const bool yp = p.Y_T != 0;
+    if (yp && !conv_gemm_a4_x3_pitched_ok(p)) return hipErrorInvalidValue;
 #ifndef VP3D_ABLATION
     if (hn_tail > 0) {
         // the whole rounds walked as without the tail (the 1x1 + residual layers)
         const int wc = walk_mode > 0 && p.R != nullptr ? a4_cus() : 0;
         if (ix) {
             a4_launch_hn<_Float16, 1, true>(p, hn_tail, stream, wc, hn_level);
+            return hipGetLastError();
+        }
+        if (yp) {
+            a4_launch_hn<_Float16, 1, false, true>(p, hn_tail, stream, wc, hn_level);
             return hipGetLastError();
         }
         if (a4_tail_split(p, hn_tail, hn_level, true)) {
@@ -1521,7 +1570,7 @@ hipError_t launch_conv_gemm_a4_x3(const ConvGemmParams& p_in, bool out_f32, hipS
         const char* e = getenv("VP3D_ABL");
         return e ? atoi(e) : 0;
     }();
-    if (abl && !out_f32 && !split) {
+    if (abl && !out_f32 && !split && !yp) {
         switch (abl) {
             case 1: a4_x3_abl<1>(p, grid); break;
             case 2: a4_x3_abl<2>(p, grid); break;
@@ -1537,6 +1586,8 @@ hipError_t launch_conv_gemm_a4_x3(const ConvGemmParams& p_in, bool out_f32, hipS
 #endif
     if (ix)
         a4_launch<_Float16, 1, true>(p, grid, false, stream);
+    else if (yp)  // (whole tiles, never split: conv_gemm_a4_x3_pitched_ok)
+        hipLaunchKernelGGL((conv_gemm_a4<_Float16, 0, 1, true, false, 0, false, true>), grid, dim3(256), 0, stream, p);
     else if (out_f32)
         a4_launch<_Float16, 2>(p, grid, split, stream);
     else

@@ -28,6 +28,10 @@
 //   gather_table_rows  the windows' rows copied out of the table into the contiguous
 //                       (B, T_out) layout the expand conv itself writes (kernel forms without
 //                       indirect windows; the bit-identity reference of the tests)
+//   replicate_edge_rows the clamp-constant edge rows of a frame table level (vp3d_capi.cpp,
+//                       plan_table_edges): the level's convs computed rows a .. b of every
+//                       sequence only; rows below a are copies of row a (every frame clamps to
+//                       frame 0), rows above b of row b (every frame clamps to the last one)
 #include "kernels.h"
 
 namespace vp3d {
@@ -87,7 +91,34 @@ __global__ __launch_bounds__(256) void gather_table_rows_kernel(const u32x4* __r
     }
 }
 
+// replica r of a sequence (a + pitch - 1 - b of them): row r < a takes row a, row b + 1 + (r - a)
+// takes row b; one replica row per workgroup trip, one 16-byte word per lane
+__global__ __launch_bounds__(256) void replicate_edge_rows_kernel(u32x4* __restrict__ table, int64_t reps, int per_seq,
+                                                                  int pitch, int a, int b, int row16) {
+    for (int64_t r = blockIdx.x; r < reps; r += gridDim.x) {
+        const int i = (int)(r / per_seq);
+        const int j = (int)(r - (int64_t)i * per_seq);
+        const int dst_row = j < a ? j : b + 1 + (j - a);
+        const int src_row = j < a ? a : b;
+        u32x4* const seq = table + (int64_t)i * pitch * row16;
+        const u32x4* src = seq + (int64_t)src_row * row16;
+        u32x4* dst = seq + (int64_t)dst_row * row16;
+        for (int c = threadIdx.x; c < row16; c += 256) dst[c] = src[c];
+    }
+}
+
 }  // namespace
+
+hipError_t launch_replicate_edge_rows(void* table, int n_seq, int pitch, int a, int b, int row_bytes, hipStream_t s) {
+    if (row_bytes % 16 != 0 || row_bytes <= 0 || n_seq <= 0 || a < 0 || b < a || b >= pitch) return hipErrorInvalidValue;
+    const int per_seq = a + (pitch - 1 - b);
+    if (per_seq == 0) return hipSuccess;
+    const int64_t reps = (int64_t)n_seq * per_seq;
+    const unsigned grid = (unsigned)(reps < (1 << 20) ? reps : (1 << 20));
+    hipLaunchKernelGGL(replicate_edge_rows_kernel, dim3(grid), dim3(256), 0, s, (u32x4*)table, reps, per_seq, pitch, a, b,
+                       row_bytes / 16);
+    return hipGetLastError();
+}
 
 hipError_t launch_window_bases(const int32_t* pairs, const int32_t* seq_len, int B, int n_seq, const WindowRegions& wr,
                                int lo, int lead, int32_t* base, unsigned* fault, hipStream_t s) {

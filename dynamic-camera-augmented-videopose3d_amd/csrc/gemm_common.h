@@ -67,6 +67,12 @@ __device__ __forceinline__ int res_row(const ConvGemmParams& p, int m) {
     return b * p.R_T + t * p.R_stride + p.R_off;
 }
 
+// the output row of GEMM row m under an output window pitch (ConvGemmParams::Y_T > 0)
+__device__ __forceinline__ int out_row(const ConvGemmParams& p, int m) {
+    const int b = m / p.T_out;
+    return b * p.Y_T + (m - b * p.T_out);
+}
+
 // Indirect windows (conv_gemm_a4; the expand table of vp3d_capi.cpp): an operand whose window
 // pitch T (ConvGemmParams::T_in for A, R_T for the split-fp16 residual) is negative holds its
 // windows at arbitrary rows of one shared table -- window b starts at row base[b], base = the

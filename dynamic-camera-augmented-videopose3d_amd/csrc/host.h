@@ -148,6 +148,9 @@ struct vp3d_handle {
     unsigned* tab_hint_host = nullptr;
     unsigned* tab_hint_dev = nullptr;
     int tab_layout = 0;
+    // per table level of the last gathered forward: (first computed row, rows computed, pitch) of
+    // the main region (vp3d_capi.cpp, plan_table_edges; vp3d_table_rows)
+    std::vector<int> tab_rows;
     // split-K workspace of conv_gemm_a4 (ConvGemmParams::sk_part / sk_flag), allocated on the
     // first forward whose plan splits a layer; flags zeroed then, each owner unit takes its
     // helpers' counts back out (and vp3d_sync_status re-zeroes them after a reported timeout)

@@ -55,6 +55,12 @@ struct ConvGemmParams {
     // forward whose window_bases_kernel met a start the main region does not serve.  Null: no gate.
     const unsigned* gate;
     unsigned gate_serial;
+    // conv_gemm_a4, the f16x3 1x1 + residual layers on the direct (not indirect) tile forms only:
+    // the output's window pitch.  0: output rows packed, row m at Y + m ldy, as everywhere else.
+    // > 0: output row m at row (m / T_out) Y_T + m % T_out -- the launch that computes rows
+    // a .. b of every sequence of a frame table level from packed k-conv rows and writes them into
+    // the level at the table's pitch (vp3d_capi.cpp, plan_table_edges), Y advanced by a rows.
+    int Y_T;
 };
 
 // split-K control block at byte kSplitCtlOffset of the flag area (ConvGemmParams::sk_flag)
@@ -114,6 +120,10 @@ hipError_t launch_conv_gemm_a4_x3(const ConvGemmParams& p, bool out_f32, hipStre
 // `any_fill`: without a4's tile-count rule (the block that reads a frame table: a launch of
 // fewer tiles than a4 otherwise takes runs them as one partial round).
 bool conv_gemm_a4_x3_indirect_ok(const ConvGemmParams& p, bool any_fill = false);
+// Pitched output (ConvGemmParams::Y_T > 0): taken by launch_conv_gemm_a4_x3 for a 1x1 + residual
+// layer over direct windows, split rows out, without a split workspace -- whole tiles with a
+// half-N / quarter-N tail at most; output bytes at the pitch < 2^31 - 64 KiB.
+bool conv_gemm_a4_x3_pitched_ok(const ConvGemmParams& p);
 // Split-K tail of an a4 launch (conv_gemm_tail.hip): rows [m_begin, M) as (N / 64) x S
 // K-slices of 256 x 64 over `ncu` CUs, f32 partials in p.sk_part (the split workspace), then
 // one reduction launch with a4's epilogue -- the split-fp16 one (x3) or the 16-bit one (bf16 /
@@ -404,6 +414,11 @@ hipError_t launch_window_bases(const int32_t* pairs, const int32_t* seq_len, int
                                int lo, int lead, int32_t* base, unsigned* fault, hipStream_t s);
 hipError_t launch_gather_table_rows(const void* table, const int32_t* base, int B, int T_out, int s0,
                                     int row_bytes, void* out, hipStream_t s);
+// Frame table levels whose clamp-constant edge rows are not computed (vp3d_capi.cpp,
+// plan_table_edges): in every one of `n_seq` sequences of `pitch` rows, row `a` copied into rows
+// 0 .. a - 1 and row `b` into rows b + 1 .. pitch - 1 (0 <= a <= b < pitch; rows of row_bytes, a
+// multiple of 16)
+hipError_t launch_replicate_edge_rows(void* table, int n_seq, int pitch, int a, int b, int row_bytes, hipStream_t s);
 hipError_t launch_pose_metrics(const float* pred, const float* target, int64_t n_frames, int J, double* acc,
                                hipStream_t s);
 

@@ -528,6 +528,9 @@ struct TablePlan {
     int max_len = 0;
     int edge_row0 = 0;
     std::vector<int> epitch;
+    // The main-region rows the convs of level l compute (plan_table_edges): row_a[l] .. row_b[l];
+    // the rows outside are copies of those two (0 .. pitch[l] - 1: every row computed).
+    std::vector<int> row_a, row_b;
 };
 // Table rows may number at most 1 / kTableFactor of the window rows they replace: the margin the
 // table paths were introduced with, never measured, and kept wherever no measurement covers it --
@@ -781,6 +784,57 @@ void plan_table_layout(const vp3d_handle* h, const std::vector<int>& len, const 
     tp.table_bytes = (size_t)rows * 2 * C * 2;
 }
 
+// Which main-region rows of the frame-table levels 1 .. depth the convs compute (either layout;
+// `first` = the start row 0 of the region stands for, tp.main_lo).  Row q of level l is a function
+// of the frames first + q - lead .. first + q - lead + S_l, clamped to the sequence (S_l: the frame
+// span of a level-l row minus 1: S_0 = taps_0 - 1, S_l = S_{l-1} + (taps_l - 1) dil_l step_{l-1}; 2,
+// 8, 26, 80 for the 243-frame model).  Where that span ends at or before frame 0 every frame clamps
+// to frame 0, and where it begins at or after frame max_len - 1 >= len_i - 1 every frame clamps to
+// the sequence's last one -- in every sequence -- so
+//   a_l = the largest q with first + q - lead + S_l <= 0   (0 if none),
+//   b_l = the smallest q with first + q - lead >= max_len - 1   (pitch_l - 1 if none),
+// rows < a_l equal row a_l and rows > b_l equal row b_l: the level's k-conv computes rows a_l ..
+// b_l packed, its 1x1 + residual writes them into the level at the table's pitch
+// (ConvGemmParams::Y_T), and launch_replicate_edge_rows fills the rest.  A replica is a copy of a
+// row the same instruction chain computed from the same inputs: the same bits.  Level 0 (the
+// expand fill) and the gated edge segments keep every row.  VP3D_TABLE_EDGES=0 keeps every row
+// everywhere; a level keeps them where the shortened launches would leave the a4 tile forms.
+void plan_table_edges(const vp3d_handle* h, const GatherSrc* gs, int n_seq, TablePlan& tp) {
+    tp.row_a.assign((size_t)tp.depth + 1, 0);
+    tp.row_b.resize((size_t)tp.depth + 1);
+    for (int l = 0; l <= tp.depth; ++l) tp.row_b[l] = tp.pitch[l] - 1;
+    if (tp.mode != 1 || tp.depth == 0) return;
+    if (const char* e = getenv("VP3D_TABLE_EDGES"))
+        if (atoi(e) == 0) return;
+    const Layer& L0 = h->layers[0];
+    int64_t S = (int64_t)(L0.taps - 1) * L0.dil;
+    for (int l = 1; l <= tp.depth; ++l) {
+        const Layer &Lk = h->layers[2 * l - 1], &Lp = h->layers[2 * l];
+        const int st = tp.step[l - 1], pin = tp.pitch[l - 1], pout = tp.pitch[l];
+        S += (int64_t)(Lk.taps - 1) * Lk.dil * st;
+        const int64_t a64 = (int64_t)gs->lead - tp.main_lo - S;
+        const int64_t b64 = (int64_t)tp.max_len - 1 + gs->lead - tp.main_lo;
+        const int a = (int)std::min<int64_t>(std::max<int64_t>(a64, 0), pout - 1);
+        const int b = (int)std::min<int64_t>(std::max<int64_t>(b64, a), pout - 1);
+        if (a == 0 && b == pout - 1) continue;
+        const int rows = b - a + 1;
+        // the shortened launches: the k-conv's rows packed, the 1x1's out at the table's pitch
+        ConvGemmParams q = x3_probe(Lk, 0, 0, 0);
+        table_layer_geometry(q, Lk, n_seq, pin, st);
+        q.M = n_seq * rows;
+        q.T_out = rows;
+        ConvGemmParams r = x3_probe(Lp, 0, 0, 0);
+        table_layer_geometry(r, Lp, n_seq, rows, st);
+        table_residual_geometry(r, Lp, pin, st);
+        r.Y_T = pout;
+        if (!vp3d::conv_gemm_a4_x3_eligible(q, false) || !vp3d::conv_gemm_a4_x3_eligible(r, false) ||
+            !vp3d::conv_gemm_a4_x3_pitched_ok(r))
+            continue;
+        tp.row_a[l] = a;
+        tp.row_b[l] = b;
+    }
+}
+
 // one table slot: [bases | table]; b_pad % 64 == 0 and whole 16-byte rows keep every slot aligned
 size_t table_slot_bytes(const TablePlan& tp) { return (size_t)tp.b_pad * 4 + tp.table_bytes; }
 
@@ -1013,10 +1067,19 @@ static int forward_impl(vp3d_handle* h, const float* x, int B, int T, float* y, 
         const char* xe = getenv("VP3D_X3_EXPAND");
         if ((xe && strcmp(xe, "pack") == 0) || !expand_gemm_x3_eligible(tab_p, &tab_gs)) tp = TablePlan{};
     }
+    // the rows of levels 1 .. depth between their clamp-constant edge rows (after the last place
+    // the plan can be dropped)
+    if (tp.mode) plan_table_edges(h, gs, n_seq, tp);
     if (gs) {
         h->tab_mode = tp.mode;
         h->tab_depth = tp.depth;
         h->tab_layout = tp.mode ? (tp.trimmed ? 2 : 1) : 0;
+        h->tab_rows.clear();
+        for (int l = 0; tp.mode && l <= tp.depth; ++l) {
+            h->tab_rows.push_back(tp.row_a[l]);
+            h->tab_rows.push_back(tp.row_b[l] - tp.row_a[l] + 1);
+            h->tab_rows.push_back(tp.pitch[l]);
+        }
     }
     const int buf_first = tp.mode == 1 ? 2 * tp.depth + 1 : 0;
     int rc = ensure_ws(h, B, T, dtype, buf_first);
@@ -1143,10 +1206,17 @@ static int forward_impl(vp3d_handle* h, const float* x, int B, int T, float* y, 
             p.R_off = L.res_off;
             p.ldr = L.cout;
         }
+        // a table level computed between its clamp-constant edge rows (plan_table_edges): the main
+        // launch's rows per sequence and the first of them, else 0
+        int erows = 0, erow0 = 0;
         if (tlevel) {
             // (cur_len / block_len are table pitches here)
             table_layer_geometry(p, L, n_seq, cur_len, tp.step[tlevel - 1]);
             if (L.residual) table_residual_geometry(p, L, block_len, tp.step[tlevel - 1]);
+            if (tp.row_a[tlevel] > 0 || tp.row_b[tlevel] < tp.pitch[tlevel] - 1) {
+                erow0 = tp.row_a[tlevel];
+                erows = tp.row_b[tlevel] - erow0 + 1;
+            }
         } else if (first && tp.mode) {
             p.M = tab_p.M;  // (the FLOP of the launch made: the table's fill)
         }
@@ -1157,7 +1227,8 @@ static int forward_impl(vp3d_handle* h, const float* x, int B, int T, float* y, 
             pe.layer = li;
             pe.a = get_event(h);
             pe.b = get_event(h);
-            pe.flop = 2.0 * (double)p.M * (double)p.N * (double)p.K;
+            // (the rows the launch computes)
+            pe.flop = 2.0 * (double)(erows ? n_seq * erows : p.M) * (double)p.N * (double)p.K;
             hipEventRecord(pe.a, s);
         }
         Act a_type = first ? Act::F32 : act;
@@ -1256,7 +1327,28 @@ static int forward_impl(vp3d_handle* h, const float* x, int B, int T, float* y, 
                 // the deepest level lands where the bases were written in front of (dslot above)
                 if (li == 2 * tp.depth && p.Y != tbuf[dslot])
                     return fail(VP3D_ERR_ASSERT, "the deepest frame table left the slot its window bases are in front of");
-                e = launch_conv_gemm_a4_x3(p, false, s);
+                // between the clamp-constant edge rows: the k-conv reads from row a of every sequence
+                // on and writes its rows packed; the 1x1 reads those, takes its residual slice from
+                // row a on and writes rows a .. b of the level at the table's pitch
+                ConvGemmParams pm = p;
+                if (erows) {
+                    pm.M = n_seq * erows;
+                    pm.T_out = erows;
+                    if (!L.residual) {
+                        pm.A = (const char*)p.A + (size_t)erow0 * p.lda * 2;
+                    } else {
+                        pm.T_in = erows;
+                        pm.R_off = p.R_off + erow0;
+                        pm.Y = (char*)p.Y + (size_t)erow0 * p.ldy * 2;
+                        pm.Y_T = tp.pitch[tlevel];
+                    }
+                    if (!conv_gemm_a4_x3_eligible(pm, false) || (L.residual && !conv_gemm_a4_x3_pitched_ok(pm)))
+                        return fail(VP3D_ERR_ASSERT, "frame table layer " + std::to_string(li) + " (between its edge rows) left the a4 tile forms");
+                }
+                e = launch_conv_gemm_a4_x3(pm, false, s);
+                // ... and the rows outside a .. b from rows a and b, before anything reads the level
+                if (e == hipSuccess && erows && L.residual)
+                    e = launch_replicate_edge_rows(p.Y, n_seq, tp.pitch[tlevel], erow0, erow0 + erows - 1, p.ldy * 2, s);
                 if (e == hipSuccess && tp.trimmed) {
                     // the same layer over the edge segments (two pseudo-windows per sequence at
                     // their own pitch, after the main rows of the same slots), gated
@@ -1437,6 +1529,16 @@ int vp3d_table_layout(const vp3d_handle* h, int* edges) {
     if (edges)
         *edges = h->tab_layout != 0 && h->tab_hint_host && ((volatile unsigned*)h->tab_hint_host)[1] == h->tab_serial;
     return h->tab_layout;
+}
+
+int vp3d_table_rows(const vp3d_handle* h, int level, int* first_row, int* rows, int* pitch) {
+    if (!h) return fail(VP3D_ERR_ARG, "handle is NULL");
+    if (level < 0 || (size_t)3 * level + 2 >= h->tab_rows.size())
+        return fail(VP3D_ERR_ARG, "the last gathered forward had no table level " + std::to_string(level));
+    if (first_row) *first_row = h->tab_rows[3 * level];
+    if (rows) *rows = h->tab_rows[3 * level + 1];
+    if (pitch) *pitch = h->tab_rows[3 * level + 2];
+    return VP3D_OK;
 }
 
 void vp3d_table_depth_rule(int* factor, int* ratio_num, int* ratio_den) {

@@ -44,7 +44,7 @@ EXPORTS = [
     "vp3d_weight_count", "vp3d_create", "vp3d_load_weights", "vp3d_destroy",
     "vp3d_receptive_field", "vp3d_total_causal_shift", "vp3d_out_frames",
     "vp3d_reserve", "vp3d_forward", "vp3d_forward_windows", "vp3d_forward_windows_pool",
-    "vp3d_expand_table_mode", "vp3d_frame_table_depth", "vp3d_table_layout", "vp3d_table_depth_rule",
+    "vp3d_expand_table_mode", "vp3d_frame_table_depth", "vp3d_table_layout", "vp3d_table_rows", "vp3d_table_depth_rule",
     "vp3d_sync_status", "vp3d_profile_enable",
     "vp3d_layer_count",
     "vp3d_set_x3_prescale", "vp3d_get_x3_prescale", "vp3d_x3_calibrate", "vp3d_x3_calibrate_windows",
@@ -161,6 +161,7 @@ _SIGNATURES = {
     "vp3d_expand_table_mode": (_int, [_vp]),
     "vp3d_frame_table_depth": (_int, [_vp]),
     "vp3d_table_layout": (_int, [_vp, ctypes.POINTER(_int)]),
+    "vp3d_table_rows": (_int, [_vp, _int, ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_int)]),
     "vp3d_table_depth_rule": (None, [ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_int)]),
     "vp3d_profile_enable": (_int, [_vp, _int]),
     "vp3d_sync_status": (_int, [_vp, _vp]),

@@ -138,7 +138,13 @@ class NativeLifter:
         call compute the wide layout (every start in one region).  The range guard sees the
         table rows computed, at every level: in the trimmed layout the rows of out-of-range
         starts only when the batch holds one.  VP3D_TABLE_TRIM=0|1 forces wide / trimmed;
-        table_layout() tells which the last call took and whether its edge gate fired."""
+        table_layout() tells which the last call took and whether its edge gate fired.
+
+        Clamp-constant edge rows: a table row of blocks 1 .. d whose frames all lie at or before
+        frame 0, or all at or after frame max(lengths) - 1, equals its neighbour towards the
+        sequence, so each level's convs compute only the rows between those runs and a copy kernel
+        fills the rest: still the same bits.  VP3D_TABLE_EDGES=0 computes every row;
+        table_rows(level) tells the rows the last call computed."""
         def _idx(d):
             d = torch.device(d)
             return (d.type, d.index if d.index is not None else torch.cuda.current_device())
@@ -187,6 +193,17 @@ class NativeLifter:
         e = ctypes.c_int(0)
         layout = self._lib.vp3d_table_layout(self._h, ctypes.byref(e))
         return layout, bool(e.value)
+
+    def table_rows(self, level: int):
+        """(first_row, rows, pitch) of table level `level` in the last forward_windows
+        (vp3d_table_rows; 0 = the expand table, l = block l's output): per sequence, the convs
+        computed rows first_row .. first_row + rows - 1 of the level's `pitch` main-region rows,
+        and the rows outside are copies of the first / last of them.  Raises for a level the call
+        had no table of."""
+        a, r, p = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+        N.check(self._lib.vp3d_table_rows(self._h, int(level), ctypes.byref(a), ctypes.byref(r), ctypes.byref(p)),
+                "vp3d_table_rows")
+        return a.value, r.value, p.value
 
     def table_depth_rule(self):
         """(factor, num, den) of the tables' size rule (vp3d_table_depth_rule): a table is taken

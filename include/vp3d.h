@@ -188,6 +188,14 @@ int vp3d_forward_windows(vp3d_handle* h, const float* kps, int32_t f2, const flo
  * makes the next forward on the handle take the wide layout (one region for every start, no edge
  * segments: fewer rows than main + edges) until a batch without such starts has been seen.
  * VP3D_TABLE_TRIM=0|1 (read once per forward) forces wide or trimmed; vp3d_table_layout reports.
+ * Clamp-constant edge rows: a main-region row of level l >= 1 whose frames all lie at or before
+ * frame 0, or all at or after frame max_len - 1, holds the same value as its neighbour towards the
+ * sequence in every sequence (frames clamp to the sequence's first / last one), so each level's
+ * launches compute the rows a_l .. b_l between those runs only and a small copy kernel fills the
+ * rest from rows a_l and b_l -- the same bits (113 / 95 / 41 rows per side of levels 1 / 2 / 3 at
+ * max_len 2,048, lead 121).  VP3D_TABLE_EDGES=0|1 (read once per forward; default 1) turns that
+ * off / on; a level whose shortened launch would leave the a4 tile forms keeps its full rows;
+ * vp3d_table_rows reports.
  * A forward that takes a table must not be captured into a hipGraph: its launches carry the
  * forward's serial number as an argument, and a replay after a later forward on the handle would
  * skip the edge launches its own bases may point into (graph capture is vp3d_forward's only).
@@ -217,6 +225,13 @@ int vp3d_frame_table_depth(const vp3d_handle* h);
  * layout, when its edge gate fired; valid once the forward has completed (synchronise first).
  * -1 for a NULL handle.  (Diagnostics and tests.) */
 int vp3d_table_layout(const vp3d_handle* h, int* edges);
+/* The main-region rows of table level `level` (0 = the expand table, l = block l's output, up to
+ * vp3d_frame_table_depth) that the convs of the handle's last gathered forward computed, per
+ * sequence: rows *first_row .. *first_row + *rows - 1 of the *pitch rows a sequence has at that
+ * level; the rows outside are copies of the first / last computed row (clamp-constant edge rows,
+ * above).  *rows == *pitch: every row computed.  Each pointer may be NULL.  VP3D_OK, or
+ * VP3D_ERR_ARG for a NULL handle or a level the forward had no table of.  (Diagnostics and tests.) */
+int vp3d_table_rows(const vp3d_handle* h, int level, int* first_row, int* rows, int* pitch);
 /* The size rule of the table paths: a table (the expand table, each frame-table level) is taken
  * when its nominal rows are at most 1 / *factor of the window rows it replaces where its launch is
  * shorter than one round of 256 x 256 tiles, and at most *ratio_num / *ratio_den of them where it
